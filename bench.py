@@ -1,13 +1,17 @@
 """bench.py -- SDXL-base denoising-step benchmark of the MI355X hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one DDIM denoising step of one 1024x1024 image per GPU: SDXL-base UNet forward on the classifier-free-
 guidance pair (batch 2, 4x128x128 latents, 77 text tokens) + CFG combine + DDIM update, bfloat16, replayed as one HIP
 graph.  The default workload is the north star's TARGET, BASELINE.json configs[2]: two rank-16 LoRAs on all 722
-transformer Linears + IP-Adapter injected through Adapter.inject(); `--workload bare` is configs[1] (also measured by the
-default run and reported under `extra.configs1_bare`), `--workload control --images-per-gpu 4` configs[3]'s per-GPU shape.
+transformer Linears + IP-Adapter injected through Adapter.inject(); `--workload bare` is configs[1] (also measured by a
+`--full` run and reported under `extra.configs1_bare`), `--workload control --images-per-gpu 4` configs[3]'s per-GPU shape.
+A plain run sets up, warms up, times exactly K steps, writes the last timed step's output (`x_next.npy`, float32) under
+`--dump-outputs DIR` if given, and prints the line.  `--full` adds everything else after the timed region: the per-family
+roofline replay, the CPU baseline, the bf16 parity point against the reference-written step, the other LoRA mode, the
+throughput points, the VAE decode, configs[0] / [1] / [3] / [4] and, for N > 1, the replica check.
 Weights are random-init of the real architecture, inputs synthetic, both resident in HBM before the timed region.
 Multi-GPU: one process per GPU, independent prompts per rank (weak scaling), ONE RCCL broadcast of the weights at
 start-up, no per-step collective; `python bench.py --gpus N` without a torchrun environment re-launches itself through
@@ -20,6 +24,7 @@ import json
 import os
 import re
 import socket
+import subprocess
 import sys
 import time
 from pathlib import Path
@@ -83,14 +88,14 @@ def op_flops(entry) -> float:
 
 
 def respawn_under_torchrun(n: int) -> None:
-    """`python bench.py --gpus N` (N > 1) outside a torchrun environment: become `python -m torch.distributed.run ...` with
-    the same arguments, one rank per GPU, rendezvous on 127.0.0.1 (the container hostname may not resolve)."""
+    """`python bench.py --gpus N` (N > 1) outside a torchrun environment: run `python -m torch.distributed.run ...` with the same
+    arguments as a child process (one rank per GPU, rendezvous on 127.0.0.1: the container hostname may not resolve) and exit with its status."""
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1", "--master-port", str(port),
            str(Path(__file__).resolve()), *sys.argv[1:]]
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.run(cmd).returncode)
 
 
 def pmc_mfma_file(family: str) -> Path:
@@ -276,13 +281,15 @@ def timed_steps(pipe, steps: int, warmup: int, world: int, dev: torch.device) ->
         torch.distributed.barrier()
     sync()
     t1 = time.perf_counter()
+    out = None
     for i in range(steps):
-        pipe.step(i % 50)
+        out = pipe.step(i % 50)
     sync()
     if world > 1:
         torch.distributed.barrier()
     mine = time.perf_counter() - t1
     timed_steps.last_local_s = mine  # this rank's own clock (bench.py gathers them into extra.per_rank_ms_per_step)
+    timed_steps.last_out = out  # what the last timed step returned (bench.py --dump-outputs)
     return parallel.max_over_ranks(mine, device=dev)
 
 
@@ -604,6 +611,16 @@ def sam_point(dev: torch.device, dtype: torch.dtype) -> dict:
             "launches": fast.stats["step_ops"], "fallback_nodes": fast.stats["fallback_nodes"], "output_finite": bool(torch.isfinite(y.float()).all())}
 
 
+def dump_outputs(out_dir: Path, arrays: dict) -> None:
+    """--dump-outputs DIR: the arrays the timed path returned in its last step, as DIR/<name>.npy in float32 (x_next: n_img x 4 x 128 x 128,
+    256 KiB per image).  The inputs are seeded (weights, adapters, latents, prompts), so two builds run with the same arguments can be compared file for file."""
+    import numpy as np
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(out_dir / f"{name}.npy", t.detach().float().cpu().numpy())
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -612,12 +629,16 @@ def main() -> None:
     ap.add_argument("--workload", choices=list(WORKLOADS), default="lora_ip",
                     help="lora_ip = BASELINE configs[2] (the north star's target, default); bare = configs[1]; control = configs[3] (use --images-per-gpu 4 for its 32-prompt / 8-GPU shape)")
     ap.add_argument("--images-per-gpu", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run what the headline figure does not need: per-family roofline replay, CPU baseline, bf16 parity point, "
+                         "the other LoRA mode, throughput points, VAE decode, configs[0] / [1] / [3] / [4] and the replica check of N > 1 (off: the timed steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0, help="intra-op threads of the CPU baseline (0 = the best of a sweep over physical / 4, / 2, physical, logical)")
     ap.add_argument("--cpu-budget", type=float, default=75.0, help="seconds of full-size CPU steps after which no further timed step is started (1 warm-up + up to 3 timed, median)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the informational extras (configs[1] line, fused-LoRA line, VAE decode, 4-images-per-GPU point)")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the per-family replay (profiler passes: the kernel table then holds the timed steps only)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the informational extras (configs[1] line, fused-LoRA line, VAE decode, 4-images-per-GPU point)")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-family replay (profiler passes: the kernel table then holds the timed steps only)")
     ap.add_argument("--dump-program", default=None, help="write the recorded step program (one entry per launch: entry point + shape class) as JSON: tools/profile_round.py")
     ap.add_argument("--packs", choices=["broadcast", "local"], default="broadcast",
                     help="N > 1: packed weights (K-blocked / merged / LayerNorm-folded copies) computed on rank 0 and broadcast (default), or computed by every rank for itself")
@@ -656,7 +677,9 @@ def main() -> None:
         bc["per_rank_ms_per_step"] = [round(float(t), 3) for t in parallel.all_gather(mine)]
     setup_s = time.time() - t0 - elapsed
     finite = bool(torch.isfinite(pipe.x.float()).all())
-    if world > 1:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), {"x_next": timed_steps.last_out})
+    if world > 1 and args.full:
         bc["replica_check"] = replica_check(pipe, specs, n_img, dev)
 
     if rank != 0:
@@ -668,7 +691,7 @@ def main() -> None:
     images_per_s = world * n_img / (ms_per_step * 1e-3 * 50)
     if args.dump_program:
         Path(args.dump_program).write_text(json.dumps([program_entry(e) for e in pipe.engine.low.step if e[0] is not None]))
-    roofline = None if args.no_roofline else family_roofline(pipe, args.workload, n_img, ms_per_step)
+    roofline = family_roofline(pipe, args.workload, n_img, ms_per_step) if args.full and not args.no_roofline else None
     stats = dict(pipe.engine.stats)
 
     extra: dict = {"params": n_params, "launches_per_step": stats["step_ops"], "prologue_launches": stats["prologue_ops"], "fallback_nodes": stats["fallback_nodes"],
@@ -677,7 +700,7 @@ def main() -> None:
 
     # ---- CPU baseline: refiners itself where its package is at hand (oracle/_ref), else the mirror's Chain forward; same adapters, one step ----
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline_step(bare_sd, specs, args.workload, args.cpu_threads, args.cpu_budget)
         except Exception as exc:  # noqa: BLE001 -- a baseline failure must not lose the measured line
@@ -689,7 +712,7 @@ def main() -> None:
             except Exception as exc:  # noqa: BLE001
                 extra["configs0_sd15_cpu"] = f"failed: {type(exc).__name__}: {exc}"
 
-    if world == 1 and n_img == 1 and not args.no_extra:
+    if world == 1 and n_img == 1 and args.full and not args.no_extra:
         # ---- the same target workload with run-time (exact-order) LoRA instead of merged weights ------------------------
         if args.workload == "lora_ip":
             try:
@@ -785,7 +808,7 @@ def main() -> None:
             except Exception as exc:  # noqa: BLE001
                 extra["throughput_operating_point"] = f"failed: {type(exc).__name__}: {exc}"
 
-    if world == 1 and n_img == 1 and not args.no_extra:
+    if world == 1 and n_img == 1 and args.full and not args.no_extra:
         # ---- BASELINE configs[3]'s per-GPU shape: ControlLora (canny), 4 prompts per GPU (UNet batch 8) ------------------------------
         try:
             note("configs[3] per-GPU shape")
@@ -813,7 +836,7 @@ def main() -> None:
         "config": {"workload": "SDXL-base UNet CFG step, 1024x1024 (latent 2x4x128x128, 77 text tokens), DDIM-50" + WORKLOADS[args.workload][1],
                    "baseline_config": WORKLOADS[args.workload][0], "images_per_gpu": n_img,
                    "parallelism": f"replica x{world} (independent prompts, weights broadcast once)", "hip_graph": use_graph,
-                   "lora_mode": args.lora_mode if args.workload != "bare" else None},
+                   "lora_mode": args.lora_mode if args.workload != "bare" else None, "full": args.full},
         "step_latency_ms": round(ms_per_step, 3),
         "parity_bf16_rel_l2": (extra.get("parity") or {}).get("parity_bf16_rel_l2"),
         "roofline": roofline, "cpu_baseline": cpu, "extra": extra,

@@ -32,7 +32,13 @@ def weights(family: str, seed: int = 0) -> dict[str, torch.Tensor]:
 
 
 def golden(case: str) -> dict[str, torch.Tensor]:
-    return load_file(str(GOLD / f"{case}.safetensors"))
+    """A fixture over the size limit of a committed file is stored as shards `<case>.safetensors`, `<case>.1.safetensors`, ...:
+    tensors of the same name are joined along dim 0, in shard order."""
+    parts = [load_file(str(GOLD / f"{case}.safetensors"))]
+    while (GOLD / f"{case}.{len(parts)}.safetensors").exists():
+        parts.append(load_file(str(GOLD / f"{case}.{len(parts)}.safetensors")))
+    names = dict.fromkeys(k for p in parts for k in p)
+    return {k: torch.cat([p[k] for p in parts if k in p]) for k in names}
 
 
 def manifest() -> dict[str, Any]:

@@ -1,5 +1,5 @@
 """Prompt encoder: CPU oracle and host mirror vs the real reference's DoubleTextEncoder;
-the re-implemented BPE tokenizer vs the reference's (build container only: needs the vocabulary file)."""
+the re-implemented BPE tokenizer vs the reference's (needs the vocabulary file of the refiners package build() stages under oracle/_ref)."""
 import json
 from pathlib import Path
 
@@ -14,7 +14,7 @@ from tests import support as S
 from tests.golden_cases import CLIP_CASE
 
 TOL = 2e-4
-REF_VOCAB = Path("/root/reference/src/refiners/foundationals/clip/bpe_simple_vocab_16e6.txt.gz")
+REF_VOCAB = Path(__file__).resolve().parent.parent / "oracle" / "_ref" / "src" / "refiners" / "foundationals" / "clip" / "bpe_simple_vocab_16e6.txt.gz"
 
 
 @pytest.fixture(scope="module")

@@ -1,4 +1,4 @@
-"""Only in the build container (skipped where /root/reference is absent): run the reference's OWN fluxion / adapter unit
+"""Only where build() staged the reference (oracle/_ref/tests, skipped otherwise): run the reference's OWN fluxion / adapter unit
 tests, unmodified, against the refiners_amd mirror (module aliases in tests/refcompat/alias_conftest.py).  This is the API
 regression suite SURVEY.md section 8(c) lists: 50 tests."""
 import os
@@ -9,11 +9,11 @@ from pathlib import Path
 
 import pytest
 
-REF_TESTS = Path("/root/reference/tests")
 ROOT = Path(__file__).resolve().parent.parent
+REF_TESTS = ROOT / "oracle" / "_ref" / "tests"
 FILES = ["fluxion/layers/test_chain.py", "fluxion/layers/test_basics.py", "fluxion/test_module.py", "adapters/test_adapter.py",
          "adapters/test_adapter_context.py", "adapters/test_lora.py", "adapters/test_range_adapter.py"]
-pytestmark = pytest.mark.skipif(not REF_TESTS.exists(), reason="the reference checkout is only present in the build container")
+pytestmark = pytest.mark.skipif(not REF_TESTS.exists(), reason="no reference unit tests staged under oracle/_ref (build() stages them where the reference checkout is present)")
 
 
 def test_reference_unit_tests_pass_on_the_mirror(tmp_path):

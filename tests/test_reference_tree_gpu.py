@@ -2,7 +2,7 @@
 through CompiledUNet on the MI355X and land on the golden outputs the reference itself produced on CPU.
 
 The reference package is found under REFINERS_SRC, else oracle/_ref/src (staged by __graft_entry__.build() in the build container;
-git-ignored, it travels to the GPU box with the snapshot like the built .so), else /root/reference/src.  It is test infrastructure:
+git-ignored, it goes wherever the built tree goes, like the built .so).  It is test infrastructure:
 nothing under refiners_amd/ or bench.py imports it.  What this covers beyond the dry-lowering equality of
 tests/test_reference_tree_cpu.py: the context plumbing against refiners' real UseContext / SetContext nodes
 (fluxion/layers/chain.py:645-720: inputs read where the nodes read them, context reset after the call), the per-call tree signature
@@ -20,14 +20,14 @@ ROOT = Path(__file__).resolve().parent.parent
 
 
 def _find_reference() -> Path:
-    for cand in (os.environ.get("REFINERS_SRC"), ROOT / "oracle" / "_ref" / "src", "/root/reference/src"):
+    for cand in (os.environ.get("REFINERS_SRC"), ROOT / "oracle" / "_ref" / "src"):
         if cand and (Path(cand) / "refiners").exists():
             return Path(cand)
     return Path("/nonexistent")
 
 
 REF = _find_reference()
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not (REF / "refiners").exists(), reason="no refiners checkout (REFINERS_SRC / oracle/_ref / /root/reference)")]
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not (REF / "refiners").exists(), reason="no refiners checkout (REFINERS_SRC / oracle/_ref)")]
 
 
 def _api():
