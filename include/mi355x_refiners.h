@@ -69,7 +69,7 @@ int mi355x_device_info(char* buf, int32_t buflen);
  * Long-K / small-MN problems (the 32x32-resolution convolutions: 320 tiles, K = 11520) can be split along K (`ksplit`).
  * Epilogue order: + bias[n] ; + rowbias[(m / rows_per_group)*ld_rowbias + n] ; geglu: v = a * gelu_erf(g) ;
  * (or v = gelu_erf(v) when geglu == 2, v = v * sigmoid(1.702 v) when geglu == 3: fl.GeLU with approximation NONE / SIGMOID,
- * src/refiners/fluxion/layers/activations.py:83-125) ;
+ * src/refiners/fluxion/layers/activations.py:83-125; v = max(v, 0) when geglu == 4: fl.ReLU) ;
  * + res[m*ldres + n] ; convert to dtype ; store out[m*ldo + n].
  */
 #define MI355X_MAX_SEG 3
@@ -106,7 +106,9 @@ typedef struct {
     const void* rowbias;    /* [M / rows_per_group][ld_rowbias] or NULL (RangeAdapter2d time-embedding bias) */
     int64_t ld_rowbias;
     int32_t rows_per_group;
-    int32_t geglu;          /* epilogue activation: 0 none, 1 GEGLU (value * gelu_erf(gate), packed rows), 2 gelu_erf, 3 quick-GELU on every column */
+    int32_t geglu;          /* epilogue activation: 0 none, 1 GEGLU (value * gelu_erf(gate), packed rows), 2 gelu_erf, 3 quick-GELU, 4 ReLU on every column
+                               (4 is newer than the other codes within ABI 7: a library built before it applies NO activation for 4, so the
+                               package must run on the library built from its own tree, which build() and build_native guarantee) */
     const void* res;        /* [M][ldres] or NULL */
     int64_t ldres;
     const void* zeros;      /* >= 256 zero bytes in device memory; required when conv == 1 */
@@ -435,6 +437,82 @@ int mi355x_cfg_ddim_step(int32_t dtype, void* x, const void* unet_out, const flo
  *   model_in[0:n] = model_in[n:2n] = s_next x'   (Solver.scale_model_input of the NEXT step on cat(x', x'); may be NULL)
  * coef = {cfg, hx, he, kx, ke, kd, kp, s_next}, eight floats in DEVICE memory; x, hist: n elements; unet_out: 2n (u then c). */
 int mi355x_cfg_linear_step(int32_t dtype, void* x, const void* unet_out, void* hist, void* model_in, const float* coef, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * SegmentAnything mask decoder (refiners_amd/csrc/sam_decoder.hip).  Token-major layouts; every operand has a BATCH stride, and a
+ * batch stride of 0 lets P prompts share one image-side operand (the first layer's K / V projections of the image embedding).
+ *
+ * mi355x_sam_attention -- softmax(Q K^T * scale) V for heads of D = 16 or 32 (mi355x_attention_general returns MI355X_ESHAPE for
+ * them).  Replaces fluxion/layers/attentions.py:60-202 (ScaledDotProductAttention, is_optimized=False) inside
+ * segment_anything/transformer.py:19-94: the self-attention of the prompt tokens (8 heads of 32), token -> image and image -> token
+ * (8 heads of 16).  q [B][Lq][ldq], k [B][Lk][ldk], v [B][Lk][ldv], out [B][Lq][ldo]; head h at columns h*D .. h*D + D - 1.
+ *   Lk <= 64 : one pass, every key of a head in LDS, one query per lane, no running maximum (any Lq: 4096 image queries per prompt);
+ *   Lq <= 64 : the keys split in chunks of 256 over workgroups, (max, sum, partial output) per chunk into ws
+ *              (B * H * ceil(Lk / 256) * Lq * (D + 2) floats, ws_floats = its size), then a second launch combines the chunks
+ *              in chunk order: no float atomics, replays are bit-equal;
+ *   otherwise MI355X_ESHAPE. */
+typedef struct mi355x_sam_attn_args {
+    int32_t dtype;
+    int32_t B, H, D, Lq, Lk;
+    const void* q;
+    int64_t ldq, q_batch_stride;
+    const void* k;
+    int64_t ldk, k_batch_stride;
+    const void* v;
+    int64_t ldv, v_batch_stride;
+    void* out;
+    int64_t ldo, o_batch_stride;
+    float scale;
+    float* ws;
+    int64_t ws_floats;
+} mi355x_sam_attn_args;
+int mi355x_sam_attention(const mi355x_sam_attn_args* a, void* stream);
+
+/* mi355x_convt2x2_ln_gelu -- LayerNorm2d + exact-erf GELU over groups of C channels of each row of x [M][ldx] (G groups per row,
+ * C a power of two <= 64; gamma / beta float32 [C]), float32 statistics.
+ *   Hs > 0 (G = 4): the rows are the pixels (p, y, x) of P images of Hs x Ws and x = the output of the GEMM [P Hs Ws, 256] x [256, 4 C] of
+ *     ConvTranspose2d(256 -> C, kernel 2, stride 2) with the bias in that GEMM's epilogue (group g = (dy, dx) = (g / 2, g % 2)): the result
+ *     of group g goes to pixel (p, 2y + dy, 2x + dx) of the NHWC output [P][2 Hs][2 Ws][ldo].  Replaces the first three steps of
+ *     DenseEmbeddingUpscaling (segment_anything/mask_decoder.py:75-112; fluxion/layers/norm.py:96-140 LayerNorm2d, activations.py GeLU).
+ *   Hs == 0: group g of row m is written in place of the input layout, out[m][g C + c] (the MaskEncoder's LayerNorm2d + GELU,
+ *     segment_anything/prompt_encoder.py:163-193, on the output of its space-to-depth GEMMs). */
+int mi355x_convt2x2_ln_gelu(int32_t dtype, const void* x, int64_t ldx, int64_t M, int32_t C, int32_t G, const float* gamma, const float* beta,
+                            float eps, void* out, int64_t ldo, int32_t Hs, int32_t Ws, void* stream);
+
+/* mi355x_sam_mask_head -- for every pixel of x = NHWC [P][Hin][Win][64] rows (ldx): ConvTranspose2d(64 -> 32, 2, 2) as
+ * [64] x [64, 4 * 32] (w: float32 [64][128], w[ci][q * 32 + co] = weight[ci][co][q / 2][q % 2], 16-byte aligned; bias float32 [32]),
+ * exact GELU, then the dot products of each output pixel's 32 channels with the prompt's nk kept hypernetwork vectors
+ * (hyper + p * hyper_batch_stride + kk * ld_hyper, 32 values each) -> out [P][nk][2 Hin][2 Win] (+ p * out_batch_stride).
+ * Replaces DenseEmbeddingUpscaling's second half and MaskPrediction's Matmul / Slicing / Reshape (segment_anything/mask_decoder.py:75-164):
+ * the [P, 32, 4 Hin Win] upscaled embedding never reaches memory. */
+typedef struct mi355x_sam_mask_head_args {
+    int32_t dtype;
+    int32_t P, Hin, Win, nk;
+    const void* x;
+    int64_t ldx;
+    const float* w;
+    const float* bias;
+    const void* hyper;
+    int64_t ld_hyper, hyper_batch_stride;
+    void* out;
+    int64_t out_batch_stride;
+} mi355x_sam_mask_head_args;
+int mi355x_sam_mask_head(const mi355x_sam_mask_head_args* a, void* stream);
+
+/* mi355x_sam_postprocess_masks -- segment_anything/utils.py:93-110 (postprocess_masks) in one launch: for N planes of in
+ * [Hin][Win] (+ n * in_plane_stride) the bilinear resize to R x R (align_corners=False), the crop to the top-left sh x sw and the
+ * bilinear resize to H x W, each output pixel evaluating both interpolations directly (4 x 4 input taps; the R x R intermediate is
+ * never stored).  out: [N][H][W] of dtype, or uint8 (v > threshold) when binarize != 0 (model.py:165-166). */
+typedef struct mi355x_sam_postprocess_args {
+    int32_t dtype;
+    int32_t N, Hin, Win, R, sh, sw, H, W;
+    const void* in;
+    int64_t in_plane_stride;
+    void* out;
+    int32_t binarize;
+    float threshold;
+} mi355x_sam_postprocess_args;
+int mi355x_sam_postprocess_masks(const mi355x_sam_postprocess_args* a, void* stream);
 
 #ifdef __cplusplus
 }

@@ -217,7 +217,7 @@ MI_DEV void tile_epilogue(const GemmP& p, f32x4 (&acc)[MT][NT], const float* row
             }
             if (EPIF(EPI_GELU, p.gelu)) {
 #pragma unroll
-                for (int e = 0; e < RUN; ++e) v[e] = p.gelu == 1 ? gelu_exact(v[e]) : quick_gelu(v[e]);
+                for (int e = 0; e < RUN; ++e) v[e] = epi_act(p.gelu, v[e]);
             }
             if (EPIF(EPI_GEGLU, p.geglu)) {
                 if constexpr (NT == 4) {
@@ -336,7 +336,7 @@ MI_DEV void tile_epilogue(const GemmP& p, f32x4 (&acc)[MT][NT], const float* row
                     float val = v[e];
                     if (bias) val += to_f32(bias[nn]);
                     if (rowbias) val += to_f32(rowbias[(int64_t)(m / p.rows_per_group) * p.ld_rowbias + nn]);
-                    if (p.gelu) val = p.gelu == 1 ? gelu_exact(val) : quick_gelu(val);
+                    if (p.gelu) val = epi_act(p.gelu, val);
                     if (res) val += to_f32(res[(int64_t)m * p.ldres + nn]);
                     if (p.out_f32) reinterpret_cast<float*>(p.out)[(int64_t)m * p.ldo + nn] = val;
                     else out[(int64_t)m * p.ldo + nn] = from_f32<T>(val);
@@ -421,7 +421,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmP p) {
                 float val = v[q];
                 if (bias) val += to_f32(bias[nn]);
                 if (rowbias) val += to_f32(rowbias[(int64_t)(m / p.rows_per_group) * p.ld_rowbias + nn]);
-                if (p.gelu) val = p.gelu == 1 ? gelu_exact(val) : quick_gelu(val);
+                if (p.gelu) val = epi_act(p.gelu, val);
                 if (res) val += to_f32(res[(int64_t)m * p.ldres + nn]);
                 const T o = from_f32<T>(val);
                 out[(int64_t)m * p.ldo + nn] = o;

@@ -62,6 +62,31 @@ class Conv2d(nn.Conv2d, WeightedModule):
         self.use_bias = use_bias
 
 
+class ConvTranspose2d(nn.ConvTranspose2d, WeightedModule):
+    """NCHW transposed convolution (reference: fluxion/layers/conv.py:64-120). `use_bias` mirrors the reference's keyword."""
+
+    def __init__(
+        self,
+        in_channels: int,
+        out_channels: int,
+        kernel_size: int | tuple[int, int],
+        stride: int | tuple[int, int] = 1,
+        padding: int | tuple[int, int] = 0,
+        output_padding: int | tuple[int, int] = 0,
+        groups: int = 1,
+        use_bias: bool = True,
+        dilation: int | tuple[int, int] = 1,
+        padding_mode: str = "zeros",
+        device: Any = None,
+        dtype: Any = None,
+    ) -> None:
+        super().__init__(
+            in_channels=in_channels, out_channels=out_channels, kernel_size=kernel_size, stride=stride, padding=padding,
+            output_padding=output_padding, dilation=dilation, groups=groups, bias=use_bias, padding_mode=padding_mode, device=device, dtype=dtype,
+        )
+        self.use_bias = use_bias
+
+
 class LayerNorm(nn.LayerNorm, WeightedModule):
     """reference: fluxion/layers/norm.py:13-46."""
 
@@ -142,6 +167,20 @@ class GeLU(Activation):
         if self.approximation is GeLUApproximation.SIGMOID:
             return x * torch.sigmoid(1.702 * x)
         return F.gelu(x, approximate=self.approximation.value)
+
+
+class Sin(Module):
+    """reference: fluxion/layers/basics.py:335-354."""
+
+    def forward(self, x: Tensor) -> Tensor:
+        return torch.sin(input=x)
+
+
+class Cos(Module):
+    """reference: fluxion/layers/basics.py:357-376."""
+
+    def forward(self, x: Tensor) -> Tensor:
+        return torch.cos(input=x)
 
 
 class GLU(Activation):

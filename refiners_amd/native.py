@@ -256,6 +256,34 @@ class GroupNormArgs(C.Structure):
     ]
 
 
+
+class SamAttnArgs(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("D", C.c_int32), ("Lq", C.c_int32), ("Lk", C.c_int32),
+        ("q", C.c_void_p), ("ldq", C.c_int64), ("q_batch_stride", C.c_int64),
+        ("k", C.c_void_p), ("ldk", C.c_int64), ("k_batch_stride", C.c_int64),
+        ("v", C.c_void_p), ("ldv", C.c_int64), ("v_batch_stride", C.c_int64),
+        ("out", C.c_void_p), ("ldo", C.c_int64), ("o_batch_stride", C.c_int64),
+        ("scale", C.c_float), ("ws", C.c_void_p), ("ws_floats", C.c_int64),
+    ]
+
+
+class SamMaskHeadArgs(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int32), ("P", C.c_int32), ("Hin", C.c_int32), ("Win", C.c_int32), ("nk", C.c_int32),
+        ("x", C.c_void_p), ("ldx", C.c_int64), ("w", C.c_void_p), ("bias", C.c_void_p),
+        ("hyper", C.c_void_p), ("ld_hyper", C.c_int64), ("hyper_batch_stride", C.c_int64),
+        ("out", C.c_void_p), ("out_batch_stride", C.c_int64),
+    ]
+
+
+class SamPostprocessArgs(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int32), ("N", C.c_int32), ("Hin", C.c_int32), ("Win", C.c_int32), ("R", C.c_int32), ("sh", C.c_int32), ("sw", C.c_int32),
+        ("H", C.c_int32), ("W", C.c_int32), ("in_", C.c_void_p), ("in_plane_stride", C.c_int64), ("out", C.c_void_p),
+        ("binarize", C.c_int32), ("threshold", C.c_float),
+    ]
+
 #: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "mi355x_abi_version",
@@ -283,6 +311,10 @@ EXPORTS = [
     "mi355x_gather_rows",
     "mi355x_pointwise_nchw",
     "mi355x_relpos_pack",
+    "mi355x_sam_attention",
+    "mi355x_convt2x2_ln_gelu",
+    "mi355x_sam_mask_head",
+    "mi355x_sam_postprocess_masks",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -333,6 +365,11 @@ def load(path: Optional[Path] = None) -> C.CDLL:
     lib.mi355x_gather_rows.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
     lib.mi355x_pointwise_nchw.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]
     lib.mi355x_relpos_pack.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    lib.mi355x_sam_attention.argtypes = [C.POINTER(SamAttnArgs), C.c_void_p]
+    lib.mi355x_convt2x2_ln_gelu.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                            C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
+    lib.mi355x_sam_mask_head.argtypes = [C.POINTER(SamMaskHeadArgs), C.c_void_p]
+    lib.mi355x_sam_postprocess_masks.argtypes = [C.POINTER(SamPostprocessArgs), C.c_void_p]
     lib.mi355x_set_option.argtypes = [C.c_char_p, C.c_int]
     lib.mi355x_attention_set_glds.argtypes = [C.c_int]
     lib.mi355x_attention_general_set_fast.argtypes = [C.c_int]
@@ -658,6 +695,7 @@ def gemm(
     res: Optional[Tensor] = None,
     geglu: bool = False,
     gelu: bool = False,
+    relu: bool = False,
     M: Optional[int] = None,
     N: Optional[int] = None,
     tile: int = 0,
@@ -699,7 +737,7 @@ def gemm(
         sg.x, sg.ldx, sg.w, sg.ldw, sg.k = t[0].data_ptr(), t[1], t[2].data_ptr(), t[3], t[4]
         sg.ksize, sg.stride, sg.ups, sg.H, sg.W, sg.kblocked = 1, 1, 1, 0, 0, t[5]
         keep.append((x, w))
-    assert not (geglu and gelu)
+    assert int(bool(geglu)) + int(bool(gelu)) + int(relu) <= 1
     if out_t is not None:
         assert out_t.dim() == 2 and out_t.stride(1) == 1 and out_t.shape[0] >= a.N - nt_begin and out_t.shape[1] >= a.M
         a.out_t, a.ldt, a.nt_begin = out_t.data_ptr(), out_t.stride(0), nt_begin
@@ -709,7 +747,7 @@ def gemm(
         a.bias = bias.data_ptr() if bias is not None else None
         a.rowbias, a.ld_rowbias, a.rows_per_group, a.res, a.ldres, a.geglu = None, 0, 1, None, 0, 0
     else:
-        _fill_epilogue(a, out, bias, rowbias, rows_per_group, res, (3 if gelu == "quick" else 2) if gelu else geglu)
+        _fill_epilogue(a, out, bias, rowbias, rows_per_group, res, (3 if gelu == "quick" else 2) if gelu else (4 if relu else geglu))
     if out_f32:
         assert out is not None and out.dtype == torch.float32
         a.out_f32 = 1
@@ -959,7 +997,7 @@ def _fill_epilogue(a: GemmArgs, out: Tensor, bias, rowbias, rows_per_group, res,
         a.res, a.ldres = res.data_ptr(), res.stride(0)
     else:
         a.res, a.ldres = None, 0
-    a.geglu = int(geglu)  # 0 none, 1 GEGLU, 2 GELU (erf), 3 quick GELU
+    a.geglu = int(geglu)  # 0 none, 1 GEGLU, 2 GELU (erf), 3 quick GELU, 4 ReLU
 
 
 def attention(
@@ -1199,6 +1237,86 @@ def pointwise_nchw(x: Tensor, w: Tensor, bias: Optional[Tensor], out: Tensor) ->
                                       B, Ci, out.shape[1], H * W), "mi355x_pointwise_nchw")
     return out
 
+
+
+# ------------------------------------------------------------------------------------------------ SAM mask decoder (csrc/sam_decoder.hip)
+def sam_attention_ws_floats(B: int, H: int, D: int, Lq: int, Lk: int) -> int:
+    """Floats of the workspace mi355x_sam_attention needs (0 in the short-key regime)."""
+    return 0 if Lk <= 64 else B * H * ((Lk + 255) // 256) * Lq * (D + 2)
+
+
+def sam_attention(q: Tensor, k: Tensor, v: Tensor, out: Tensor, num_heads: int, ws: Optional[Tensor] = None, scale: Optional[float] = None) -> Tensor:
+    """q [B|1, Lq, >= H*D], k / v [B|1, Lk, >= H*D], out [B, Lq, >= H*D]: 3-D views with a contiguous last dimension; a leading size of 1
+    (or a batch stride of 0) shares that operand across the batch.  ws: float32 workspace of sam_attention_ws_floats(...) elements."""
+    B, Lq = out.shape[0], out.shape[1]
+    Lk = k.shape[1]
+    D = out.shape[2] // num_heads if q.shape[2] == out.shape[2] else q.shape[2] // num_heads
+    for t in (q, k, v, out):
+        assert t.dim() == 3 and t.stride(2) == 1 and t.dtype == out.dtype
+    assert q.shape[1] == Lq and v.shape[1] == Lk and q.shape[0] in (1, B) and k.shape[0] in (1, B) and v.shape[0] in (1, B)
+    bs = lambda t: 0 if t.shape[0] == 1 else t.stride(0)  # noqa: E731
+    a = SamAttnArgs()
+    a.dtype = dtype_code(out.dtype)
+    a.B, a.H, a.D, a.Lq, a.Lk = B, num_heads, D, Lq, Lk
+    a.q, a.ldq, a.q_batch_stride = q.data_ptr(), q.stride(1), bs(q)
+    a.k, a.ldk, a.k_batch_stride = k.data_ptr(), k.stride(1), bs(k)
+    a.v, a.ldv, a.v_batch_stride = v.data_ptr(), v.stride(1), bs(v)
+    a.out, a.ldo, a.o_batch_stride = out.data_ptr(), out.stride(1), out.stride(0)
+    a.scale = scale if scale is not None else D ** -0.5
+    need = sam_attention_ws_floats(B, num_heads, D, Lq, Lk)
+    if need:
+        assert ws is not None and ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= need
+        a.ws, a.ws_floats = ws.data_ptr(), ws.numel()
+    _launch("mi355x_sam_attention", (C.byref(a),), "mi355x_sam_attention", keep=(ws,))
+    return out
+
+
+def convt2x2_ln_gelu(x: Tensor, C_: int, G: int, gamma: Tensor, beta: Tensor, eps: float, out: Tensor, scatter_hw: Optional[tuple[int, int]] = None) -> Tensor:
+    """LayerNorm2d + GELU over G groups of C_ channels of each row of x [M, >= G*C_]; scatter_hw = (Hs, Ws): group (dy, dx) of pixel
+    (p, y, x) goes to row (p, 2y + dy, 2x + dx) of out (the NHWC upsampled image), else to out[m, g*C_ : (g+1)*C_]."""
+    assert x.dim() == 2 and out.dim() == 2 and x.stride(1) == 1 and out.stride(1) == 1 and x.dtype == out.dtype
+    assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.numel() == C_ == beta.numel()
+    M = x.shape[0]
+    Hs, Ws = scatter_hw or (0, 0)
+    assert out.shape[0] == (4 * M if scatter_hw else M) and out.shape[1] >= (C_ if scatter_hw else G * C_)
+    _launch("mi355x_convt2x2_ln_gelu", (dtype_code(x.dtype), x.data_ptr(), x.stride(0), M, C_, G, gamma.data_ptr(), beta.data_ptr(), eps, out.data_ptr(),
+                                       out.stride(0), Hs, Ws), "mi355x_convt2x2_ln_gelu", keep=(gamma, beta))
+    return out
+
+
+def sam_mask_head(x: Tensor, P: int, Hin: int, Win: int, w: Tensor, bias: Tensor, hyper: Tensor, out: Tensor) -> Tensor:
+    """x [P*Hin*Win, >= 64] NHWC rows; w float32 [64, 128]; bias float32 [32]; hyper [P, nk, >= 32] (a view); out [P, nk, 2Hin, 2Win]."""
+    assert x.dim() == 2 and x.stride(1) == 1 and x.shape[0] == P * Hin * Win and x.shape[1] >= 64 and w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (64, 128)
+    assert bias.dtype == torch.float32 and bias.numel() == 32 and hyper.dim() == 3 and hyper.stride(2) == 1 and hyper.shape[0] == P
+    nk = hyper.shape[1]
+    assert out.dim() == 4 and tuple(out.shape[1:]) == (nk, 2 * Hin, 2 * Win) and out.stride(3) == 1 and out.stride(2) == 2 * Win and out.stride(1) == 4 * Hin * Win
+    a = SamMaskHeadArgs()
+    a.dtype = dtype_code(x.dtype)
+    a.P, a.Hin, a.Win, a.nk = P, Hin, Win, nk
+    a.x, a.ldx, a.w, a.bias = x.data_ptr(), x.stride(0), w.data_ptr(), bias.data_ptr()
+    a.hyper, a.ld_hyper, a.hyper_batch_stride = hyper.data_ptr(), hyper.stride(1), hyper.stride(0)
+    a.out, a.out_batch_stride = out.data_ptr(), out.stride(0)
+    _launch("mi355x_sam_mask_head", (C.byref(a),), "mi355x_sam_mask_head", keep=(w, bias))
+    return out
+
+
+def sam_postprocess_masks(low: Tensor, R: int, scaled: tuple[int, int], out: Tensor, threshold: Optional[float] = None) -> Tensor:
+    """low [..., Hin, Win] (contiguous planes) -> out [..., H, W]: of low's dtype, or uint8 / bool (low > threshold) when threshold is given."""
+    assert low.is_contiguous() and out.is_contiguous() and low.shape[:-2] == out.shape[:-2]
+    a = SamPostprocessArgs()
+    a.dtype = dtype_code(low.dtype)
+    a.Hin, a.Win = low.shape[-2], low.shape[-1]
+    a.N = low.numel() // (a.Hin * a.Win)
+    a.R, a.sh, a.sw, a.H, a.W = R, scaled[0], scaled[1], out.shape[-2], out.shape[-1]
+    a.in_, a.in_plane_stride, a.out = low.data_ptr(), a.Hin * a.Win, out.data_ptr()
+    if threshold is None:
+        assert out.dtype == low.dtype
+        a.binarize, a.threshold = 0, 0.0
+    else:
+        assert out.dtype in (torch.uint8, torch.bool)
+        a.binarize, a.threshold = 1, float(threshold)
+    _launch("mi355x_sam_postprocess_masks", (C.byref(a),), "mi355x_sam_postprocess_masks")
+    return out
 
 def set_glds(enabled: bool) -> None:
     """A/B switch: global_load_lds staging (default) vs register staging, for the GEMM and attention tile loaders."""
