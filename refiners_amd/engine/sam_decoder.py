@@ -446,7 +446,8 @@ class CompiledSegmentAnything:
                 self.cache.sweep()  # keep only what the new tree's first program packed
             got = (low, io, Program(low.step, self.use_graph, low=low))
             self.programs[key] = got
-            self.stats = dict(low.stats, step_ops=launches(low.step), pool_bytes=low.step_pool.bytes(), whole_fallback=None)
+        low = got[0]  # the stats of the program that runs now, also after a whole fallback of another geometry
+        self.stats = dict(low.stats, step_ops=launches(low.step), pool_bytes=low.step_pool.bytes(), whole_fallback=None)
         return got
 
     def compute_image_embedding(self, image: Any) -> Any:

@@ -1251,8 +1251,10 @@ def sam_attention(q: Tensor, k: Tensor, v: Tensor, out: Tensor, num_heads: int, 
     B, Lq = out.shape[0], out.shape[1]
     Lk = k.shape[1]
     D = out.shape[2] // num_heads if q.shape[2] == out.shape[2] else q.shape[2] // num_heads
+    assert D in (16, 32), f"head width {D}: mi355x_sam_attention takes D = 16 or 32"
     for t in (q, k, v, out):
         assert t.dim() == 3 and t.stride(2) == 1 and t.dtype == out.dtype
+        assert t.shape[2] >= num_heads * D, f"a view of {t.shape[2]} columns for {num_heads} heads of {D}: the kernel would read past it"
     assert q.shape[1] == Lq and v.shape[1] == Lk and q.shape[0] in (1, B) and k.shape[0] in (1, B) and v.shape[0] in (1, B)
     bs = lambda t: 0 if t.shape[0] == 1 else t.stride(0)  # noqa: E731
     a = SamAttnArgs()

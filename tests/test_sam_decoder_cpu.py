@@ -250,3 +250,25 @@ def test_unsupported_embedding_geometry_is_refused():
         SAMDecoderLowering(torch.device("meta"), torch.float32).check(sam)
     with pytest.raises(Unsupported):
         _dry(SegmentAnythingH(device="meta"), 1, 70, False, torch.float32)  # more than 64 prompt tokens
+
+
+# ------------------------------------------------------------------------------------------------ wrapper checks
+def test_sam_attention_wrapper_refuses_narrow_views_and_head_widths(monkeypatch):
+    """native.sam_attention refuses a q / k / v / out view narrower than H*D columns (the kernel would read or write past it) and a head
+    width other than 16 or 32, before anything reaches the library (CPU tensors; a launch would fail the test)."""
+    from refiners_amd import native
+
+    monkeypatch.setattr(native, "_launch", lambda *a, **k: pytest.fail("the wrapper launched"))
+    H, D, Lq, Lk = 8, 16, 5, 300
+    q, out = torch.zeros(1, Lq, H * D + 8)[..., : H * D], torch.zeros(1, Lq, H * D)
+    kv = torch.zeros(1, Lk, 2 * H * D)
+    k, v = kv[..., : H * D], kv[..., H * D :]
+    ws = torch.zeros(native.sam_attention_ws_floats(1, H, D, Lq, Lk))
+    for args in ((q, kv[..., : H * D - 8], v, out), (q, k, kv[..., H * D : 2 * H * D - 1], out), (q, k, v, out[..., : H * D - 8])):
+        with pytest.raises(AssertionError, match="columns"):
+            native.sam_attention(*args, H, ws=ws)
+    with pytest.raises(AssertionError):  # (a narrower q than out reads as another head width)
+        native.sam_attention(q[..., : H * D - 1], k, v, out, H, ws=ws)
+    narrow = torch.zeros(1, Lq, 64)
+    with pytest.raises(AssertionError, match="head width 8"):
+        native.sam_attention(narrow, kv[..., :64], kv[..., 64:128], narrow.clone(), 8, ws=ws)
