@@ -61,15 +61,17 @@ extern "C" int mi355x_set_option(const char* name, int value) {
     return MI355X_EARG;
 }
 
-static int g_stat_g8 = 0, g_stat_g8_lora = 0, g_stat_g9 = 0, g_stat_g11 = 0;
+static int g_stat_g8 = 0, g_stat_g8_lora = 0, g_stat_g9 = 0, g_stat_g11 = 0, g_stat_g12 = 0;
 extern "C" int mi355x_get_stat(const char* name);
 extern "C" int mi355x_get_stat(const char* name) {
     // launches since the library was loaded (tests: did the configuration asked for really run?); like mi355x_set_option not part of the stable contract
-    //   "g8" = launches on the 8-wave loop (tile configurations 7 / 8 / 9), "g8lora" = those of them with the in-launch LoRA, "g9" = those on 192-row tiles
+    //   "g8" = launches on the 8-wave loop (tile configurations 7 / 8 / 9), "g8lora" = those of them with the in-launch LoRA, "g9" = those on 192-row tiles,
+    //   "g11" / "g12" = those on tile configuration 11 / 12
     if (!name) return MI355X_EARG;
     if (name[0] == 'g' && name[1] == '8') return name[2] == 'l' ? g_stat_g8_lora : g_stat_g8;
     if (name[0] == 'g' && name[1] == '9') return g_stat_g9;
     if (name[0] == 'g' && name[1] == '1' && name[2] == '1') return g_stat_g11;
+    if (name[0] == 'g' && name[1] == '1' && name[2] == '2') return g_stat_g12;
     return MI355X_EARG;
 }
 
@@ -240,9 +242,19 @@ extern "C" int mi355x_gemm(const mi355x_gemm_args* a, void* stream) {
         }
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int tile_req = g_tile ? g_tile : a->tile;
-    int g8_mt = tile_req == 9 ? 6 : tile_req == 10 ? 4 : 8;  // tile 9: the same loop on 192 x 256 tiles (whole tiles only); 10: on 128 x 256 tiles (bf16 GEMMs)
-    bool want_g8 = tile_req == 7 || tile_req == 8 || tile_req == 9 || (tile_req == 10 && a->dtype == MI355X_BF16 && !a->conv);
+    int tile_req = g_tile ? g_tile : a->tile;
+    if (tile_req == 0 && a->dtype == MI355X_BF16 && p.ksplit == 1 && p.N % 320 == 0 && p.N % 256 != 0) {
+        // nobody chose: where 256-column tiles waste MFMA work (N = 320 / 640 / 960 / 1920) and 128 x 320 tiles of the 8-wave loop fill the CUs in whole rounds
+        // (the level-1 convolutions of a CFG pair: 256 tiles), those -- hot 1.1-1.4x, in place -0.3 ms per step over the six classes
+        int dev = 0, ncu = 0;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+        const int64_t t12 = (int64_t)((p.M + 127) / 128) * (p.N / 320);
+        if (ncu > 0 && t12 % ncu == 0 && gemm8_ok(p, a->conv != 0, 12)) tile_req = 12;
+    }
+    int g8_mt = tile_req == 9 ? 6 : tile_req == 10 ? 4 : tile_req == 12 ? 12 : 8;  // tile 9: the same loop on 192 x 256 tiles (whole tiles only); 10: on 128 x 256 tiles (bf16 GEMMs);
+                                                                                  // 12: on 128 x 320 tiles (bf16 GEMMs and convolutions)
+    bool want_g8 = tile_req == 7 || tile_req == 8 || tile_req == 9 || (tile_req == 10 && a->dtype == MI355X_BF16 && !a->conv) || (tile_req == 12 && a->dtype == MI355X_BF16);
     if (tile_req == 11) {  // 192-row tiles for a whole number of rounds + 128-row tiles for a whole number of rounds (bf16 GEMMs whose shape admits it: plan_mix); else tile 9
         int rb, cb, nb, ns, dev = 0, ncu = 0;
         (void)hipGetDevice(&dev);
@@ -265,6 +277,7 @@ extern "C" int mi355x_gemm(const mi355x_gemm_args* a, void* stream) {
         if (p.lora_b) ++g_stat_g8_lora;
         if (g8_mt == 6) ++g_stat_g9;
         if (g8_mt == 11) ++g_stat_g11;
+        if (g8_mt == 12) ++g_stat_g12;
         const bool sk = tile_req == 8 && a->sk_ws && a->sk_flags && a->sk_slots > 0 && (reinterpret_cast<uintptr_t>(a->sk_ws) & 15) == 0;
         p.sk_ws = static_cast<float*>(a->sk_ws);
         p.sk_flags = a->sk_flags;

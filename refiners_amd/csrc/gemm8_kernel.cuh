@@ -140,7 +140,7 @@ template <int NTHR_ALL> MI_DEV void prefetch_role(const GemmP& p, int tid_all) {
 #define MI355X_G8_PRIO 1  // s_setprio 1 around every MFMA cluster (guide T5: +21..39 % on this schedule)
 #endif
 
-template <typename T, bool CONV, bool LORA, int MTK, int MT2 = 0>
+template <typename T, bool CONV, bool LORA, int MTK, int MT2 = 0, int NT = 4>
 __global__ __launch_bounds__(512) void gemm8_kernel(const GemmP p) {
     // MT2 != 0 (round 6): a launch of TWO tile heights -- tiles [0, p.mix_nbig) are 32 MTK rows high, the rest 32 MT2: FF1 of a CFG pair (2048 x 10240) is exactly 256 tiles of
     // 192 x 256 + 256 tiles of 128 x 256, one of each per CU, where 440 tiles of 192 rows are 1.72 dispatch rounds paid as two (mix_coords below).
@@ -150,7 +150,14 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmP p) {
     // WR = rows per wave row (128 / 96) and QR = rows of one X half tile per wave row (64 / 48); the W side does not change.
     static_assert(MTK == 8 || MTK == 6 || MTK == 4, "wave tile rows");  // (MT = 4: 128 x 256 tiles, wave tile 64 x 64, 8 MFMAs per phase -- tile id 10, round 6: the second round of a two-height FF1)
     static_assert(MT2 == 0 || (MT2 == 4 && MTK == 6 && !CONV), "two-height launches: 192-row + 128-row tiles of a plain GEMM");
-    constexpr int BN = 256, NTHR = 512, NT = 4;
+    // NT = 16-column blocks per wave: 4 = the 256-column tiles of the header; 5 = 320-column tiles (tile id 12: 128 x 320, wave tile 64 x 80), which divide every
+    // SDXL channel width.  W half 0 is then blocks 0..2 of every wave (48 rows, 3 loads per thread), W half 1 blocks 3..4 (32 rows, 2 loads): the quadrants
+    // of a K tile are 12 / 8 / 8 / 12 MFMAs, and the counted waits keep the three youngest half tiles (7 loads) in flight.  A lane's columns: 16 consecutive
+    // ones from blocks 0..3 (MMA row 4 a + b of block j < 4 is wave column 16 a + 4 j + b, as for NT = 4), then 4 from block 4 (its row r is column 64 + r).
+    static_assert(NT == 4 || (NT == 5 && MTK == 4 && MT2 == 0 && !LORA), "320-column tiles: 128 rows, no two-height form, no in-launch LoRA");
+    constexpr int BN = 64 * NT, NTHR = 512, WC = 16 * NT;  // WC = columns (W-slot rows) per wave
+    constexpr int NW0 = NT == 5 ? 3 : 2, NW1 = 2;          // 16-row W blocks per wave in W half 0 / 1 (= loads per thread of that half tile)
+    constexpr int VMW = NW0 + NW1 + 2;                      // vmcnt of the counted waits: the three youngest half tiles W0, X0, W1
     constexpr int BUFB = (32 * MTK + BN) * 128;  // bytes of one LDS stage buffer (X tile + W tile) of the LARGER tile: the launch's LDS partition
     constexpr uint32_t OOB = 0x80000000u;                  // per-lane offset beyond every descriptor's num_records: the load writes zeros
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -297,12 +304,25 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmP p) {
         //   = 128 s + 8 h + wlane.  Rows beyond the operand get row -1 (offset 2^32 - ld + coff: beyond every descriptor, the load writes zeros).
         const int wq = 8 * (wid & 3) + lr8;
         const int xlane = 8 * wid + lr8, wlane = 64 * (wid >> 2) + 16 * ((wq >> 2) & 3) + 4 * (wq >> 4) + (wq & 3);
+        // 8-row block of the W slot that wave wid fills with load s2 of W half h (wave-uniform): half h of wave column c is its rows [c WC + h 16 NW0, + 16 NWh);
+        // load slot q = 8 s2 + wid takes block q % (2 NWh) of wave column q / (2 NWh).  The bank swizzle ((R >> 1) & 7) of its rows then is 4 (wid & 1) + (lane >> 4)
+        // as the single source-chunk offset `coff` assumes: every term but q % (2 NWh) is even, and that has the parity of wid.
+        auto w_rb = [&](int h, int s2) __attribute__((always_inline)) {
+            const int nb8 = 2 * (h ? NW1 : NW0), q = 8 * s2 + wid;
+            return (WC / 8) * (q / nb8) + 2 * NW0 * h + q % nb8;
+        };
         auto xrow = [&](int h, int s2) __attribute__((always_inline)) {
             const int r = xs_0 + WR * s2 + QR * h + xlane;
             return r < xs_lim && (MT == 8 || wid < XW) ? r : -1;  // (MT = 6: waves 6 and 7 stage nothing real -- zeros into a spare LDS area)
         };
         auto wrow = [&](int h, int s2) __attribute__((always_inline)) {
-            const int r = ws_0 + 128 * s2 + 8 * h + wlane;
+            int r;
+            if constexpr (NT == 4) {
+                r = ws_0 + 128 * s2 + 8 * h + wlane;
+            } else {  // LDS row R = 8 w_rb(h, s2) + (lane >> 3) of the W slot: wave column R / WC, and inside it block j = rl / 16, row 4 a + b of that block
+                const int R = 8 * w_rb(h, s2) + lr8, wc = R / WC, rl = R - wc * WC, j = rl >> 4, rr = rl & 15;
+                r = ws_0 + wc * WC + (j < 4 ? 16 * (rr >> 2) + 4 * j + (rr & 3) : 64 + rr);
+            }
             return r < ws_lim ? r : -1;
         };
         int xb[2][2], xyx[2][2];  // conv: image index (-1: a row beyond M), (oy | ox << 16) of the output pixel
@@ -333,7 +353,7 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmP p) {
         }
 
         // ---- two independent cursors (the X halves of a K tile are staged in other phases than its W halves) ----
-        uint32_t xvo[2][2], wvo[2][2];  // per-lane byte offsets into the current segment's x / w
+        uint32_t xvo[2][2], wvo[2][NW0];  // per-lane byte offsets into the current segment's x / w
         rsrc_t xrs, wrs;
         int x_seg = seg0, x_kb = kb0, x_nkb = 0, x_cpb = 1, x_cb = 0, x_tap = 0;
         int w_seg = seg0, w_kb = kb0, w_nkb = 0;
@@ -389,7 +409,7 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmP p) {
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) wvo[h][s2] = (uint32_t)wrow(h, s2) * ld + coff;
+                for (int s2 = 0; s2 < (h ? NW1 : NW0); ++s2) wvo[h][s2] = (uint32_t)wrow(h, s2) * ld + coff;
         };
         auto adv_x = [&]() __attribute__((always_inline)) {  // one K tile forward (called behind the stage of X half 1)
             ++x_kb;
@@ -422,13 +442,18 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmP p) {
             for (int s = 0; s < 2; ++s) blds16(xrs, MT == 8 || wid < XW ? smem + buf * BUFB + (WR * s + QR * h + 8 * wid) * 128 : spare + (wid - XW) * 1024, xvo[h][s], x_so);
         };
         auto stage_w = [&](int h, int buf) __attribute__((always_inline)) {
+            if constexpr (NT == 4) {
 #pragma unroll
-            for (int s = 0; s < 2; ++s) blds16(wrs, smem + buf * BUFB + XB + (64 * (2 * s + (wid >> 2)) + 32 * h + 8 * (wid & 3)) * 128, wvo[h][s], w_so);
+                for (int s = 0; s < 2; ++s) blds16(wrs, smem + buf * BUFB + XB + (64 * (2 * s + (wid >> 2)) + 32 * h + 8 * (wid & 3)) * 128, wvo[h][s], w_so);
+            } else {
+#pragma unroll
+                for (int s = 0; s < (h ? NW1 : NW0); ++s) blds16(wrs, smem + buf * BUFB + XB + w_rb(h, s) * 1024, wvo[h][s], w_so);
+            }
         };
 
         // ---- fragments ----
         frag_t xf[MT / 2][2];  // X quadrant rows: [16-row block][K half]
-        frag_t wf[2][2][2];  // W halves: [h][16-row block][K half]
+        frag_t wf[2][NW0][2];  // W halves: [h][16-row block][K half]
         auto read_x = [&](int h, int buf) __attribute__((always_inline)) {
             const char* xs = smem + buf * BUFB + (WR * wm + QR * h) * 128;
 #pragma unroll
@@ -437,20 +462,20 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmP p) {
                 for (int kk = 0; kk < 2; ++kk) xf[i][kk] = lds_read_frag(xs, i * 2048 + fo[kk]);
         };
         auto read_w = [&](int h, int buf) __attribute__((always_inline)) {
-            const char* ws = smem + buf * BUFB + XB + (64 * wn + 32 * h) * 128;
+            const char* ws = smem + buf * BUFB + XB + (WC * wn + 16 * NW0 * h) * 128;
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
+            for (int j = 0; j < (h ? NW1 : NW0); ++j)
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk) wf[h][j][kk] = lds_read_frag(ws, j * 2048 + fo[kk]);
         };
-        auto mma_q = [&](auto hxc, auto hwc) __attribute__((always_inline)) {  // quadrant (hx, hw): 16 MMA steps
+        auto mma_q = [&](auto hxc, auto hwc) __attribute__((always_inline)) {  // quadrant (hx, hw): 16 MMA steps (MT = 8, NT = 4)
             constexpr int hx = decltype(hxc)::value, hw = decltype(hwc)::value;
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
                 for (int i = 0; i < MT / 2; ++i)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) mma_step<T>(acc[(MT / 2) * hx + i][2 * hw + j], wf[hw][j][kk], xf[i][kk]);
+                    for (int j = 0; j < (hw ? NW1 : NW0); ++j) mma_step<T>(acc[(MT / 2) * hx + i][NW0 * hw + j], wf[hw][j][kk], xf[i][kk]);
         };
         // the compute half of a phase: barrier | the fragments have arrived | 16 MFMA at raised priority | barrier
         auto compute = [&](auto hxc, auto hwc, bool reads) __attribute__((always_inline)) {
@@ -491,7 +516,7 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmP p) {
                 colvec[tid] = to_f32(reinterpret_cast<const T*>(p.bias)[n]);
             }
         }
-        if (nk > 1) wait_vm<6>();
+        if (nk > 1) wait_vm<VMW>();
         else wait_vm0();
         stamp();  // (1) first K tile landed
         fence();
@@ -523,7 +548,7 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmP p) {
             if (e2) {
                 stage_w(1, 0);
                 adv_w();
-                wait_vm<6>();
+                wait_vm<VMW>();
             } else {
                 wait_vm0();
             }
@@ -549,7 +574,7 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmP p) {
             if (e3) {
                 stage_w(1, 1);
                 adv_w();
-                wait_vm<6>();
+                wait_vm<VMW>();
             } else {
                 wait_vm0();
             }
@@ -678,6 +703,18 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmP p) {
             for (int i = 0; i < MT; ++i)
 #pragma unroll
                 for (int j = 0; j < NT; ++j) asm volatile("" ::"v"(acc[i][j]));
+        } else if constexpr (NT == 5) {
+            // a lane's 20 columns in two parts: blocks 0..3 (16 consecutive columns, two 16-byte runs per row) and block 4 (4 columns, one 8-byte run)
+            constexpr unsigned AL = EPI_RB | EPI_GELU | EPI_RES | EPI_CS;  // (gemm8_ok keeps LayerNorm-folded, GEGLU, row-statistics and float32 launches off these tiles)
+            f32x4 a4[MT][4], a1[MT][1];
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a4[i][j] = acc[i][j];
+                a1[i][0] = acc[i][4];
+            }
+            tile_epilogue<T, MT, 4, BM, CONV, false, true, WC, 0, BN, AL>(pq, a4, rowstat, m0, n0, wm, wn, lane_e, false, 0, colvec);
+            tile_epilogue<T, MT, 1, BM, CONV, false, true, WC, 64, BN, AL>(pq, a1, rowstat, m0, n0, wm, wn, lane_e, false, 0, colvec);
         } else if constexpr (!CONV) {
             if (MT == 8 && tr) {  // the transposed tile's blocks: 4 x 8 over (activation rows of wave column wn, weight rows of wave row wm)  (256-row tiles only: gemm8_ok)
                 f32x4 at[NT][MT];
@@ -733,11 +770,12 @@ inline bool plan_mix(int M, int N, int n_cu, int& rb, int& cb, int& nbig, int& n
     return false;
 }
 
-template <typename T, bool CONV, bool LORA, int MT, int MT2 = 0>
+template <typename T, bool CONV, bool LORA, int MT, int MT2 = 0, int NT = 4>
 int launch_gemm8_impl(const GemmP& p, hipStream_t stream, bool streamk) {
-    constexpr int LDS = 2 * (32 * MT + 256) * 128 + 2 * (256 * 8 + 2 * 256 * 4) + (MT == 4 || MT2 == 4 ? 4096 : 2048);  // two stage buffers + two sets of epilogue vectors + the spare landing area (1 KB per wave without X rows)
-    static_assert(LDS <= 160 * 1024, "LDS budget");
-    auto kfn = gemm8_kernel<T, CONV, LORA, MT, MT2>;
+    constexpr int BN = 64 * NT;
+    constexpr int LDS = 2 * (32 * MT + BN) * 128 + 2 * (256 * 8 + 2 * BN * 4) + (MT == 4 || MT2 == 4 ? 4096 : 2048);  // two stage buffers + two sets of epilogue vectors + the spare landing area (1 KB per wave without X rows)
+    static_assert(LDS <= 160 * 1024, "LDS budget");  // (128 x 320: 112 KB of stage buffers + 9 KB + 4 KB = 125 KB)
+    auto kfn = gemm8_kernel<T, CONV, LORA, MT, MT2, NT>;
     static bool attr_set[64] = {};
     static int n_cu[64] = {};
     int dev = 0;
@@ -748,7 +786,7 @@ int launch_gemm8_impl(const GemmP& p, hipStream_t stream, bool streamk) {
         attr_set[dev] = true;
     }
     GemmP q = p;
-    plan_grid(q, 32 * MT, 256, CONV, 2);
+    plan_grid(q, 32 * MT, BN, CONV, 2);
     q.lora_dbg = g_lora_dbg & 1;  // (mi355x_set_option "lora_dbg"; the other probing bits belong to the 4-wave kernel's producers)
     q.lora_tt = 0;
     // producers: one per 32 rows, two to a workgroup for ranks 32 / 64 (see the kernel), padded to a multiple of 8 workgroups (tile b stays on XCD b % 8)
@@ -760,7 +798,7 @@ int launch_gemm8_impl(const GemmP& p, hipStream_t stream, bool streamk) {
     q.sk_g = q.grid0;  // one tile per workgroup
     int ncu = dev >= 0 && dev < 64 && n_cu[dev] > 0 ? n_cu[dev] : 256;
     if (g_sk_g > 0) ncu = g_sk_g;
-    if (streamk && !q.lora_b && q.sk_ws && q.sk_flags && q.grid0 % ncu != 0) {
+    if (streamk && NT == 4 && !q.lora_b && q.sk_ws && q.sk_flags && q.grid0 % ncu != 0) {  // (a stream-K slot holds a 256 x 256 float32 tile)
         // "stream-K": one persistent workgroup per CU (256 on MI355X; the decomposition -- hence the summation order -- depends on this number only),
         // fewer when there is less than two K tiles of work for each
         int G = ncu;
@@ -816,7 +854,12 @@ int launch_gemm8_impl(const GemmP& p, hipStream_t stream, bool streamk) {
 }
 
 template <typename T, bool CONV>
-int launch_gemm8(const GemmP& p, hipStream_t stream, bool streamk, int mt) {  // mt: 8 = 256-row tiles (tile ids 7 / 8), 6 = 192-row tiles (tile id 9), 4 = 128-row tiles (tile id 10: bf16 GEMMs only), 11 = 192- and 128-row tiles in one launch (tile id 11)
+int launch_gemm8(const GemmP& p, hipStream_t stream, bool streamk, int mt) {  // mt: 8 = 256-row tiles (tile ids 7 / 8), 6 = 192-row tiles (tile id 9), 4 = 128-row tiles (tile id 10: bf16 GEMMs only), 11 = 192- and 128-row tiles in one launch (tile id 11),
+                                                                                //     12 = 128 x 320 tiles (tile id 12: bf16 GEMMs and convolutions, whole tiles)
+    if (mt == 12) {
+        if constexpr (sizeof(T) == 2) return launch_gemm8_impl<T, CONV, false, 4, 0, 5>(p, stream, false);
+        return MI355X_ESHAPE;
+    }
     if constexpr (!CONV && sizeof(T) == 2) {
         if (mt == 11) return p.lora_b ? launch_gemm8_impl<T, false, true, 6, 4>(p, stream, false) : launch_gemm8_impl<T, false, false, 6, 4>(p, stream, false);
         if (mt == 4) return p.lora_b ? launch_gemm8_impl<T, false, true, 4>(p, stream, false) : launch_gemm8_impl<T, false, false, 4>(p, stream, false);
@@ -833,6 +876,8 @@ int launch_gemm8(const GemmP& p, hipStream_t stream, bool streamk, int mt) {  //
 // 2 GB: 32-bit buffer offsets with 0x80000000 as the out-of-range marker.)
 inline bool gemm8_ok(const GemmP& p, bool conv = false, int mt = 8) {
     if (mt != 8 && p.out_t) return false;  // (the 192- and 128-row tiles have no transposed form)
+    // (the 320-column tiles run the plain, bias, row-bias, activation, residual and column-statistics epilogues, without in-launch LoRA)
+    if (mt == 12 && (p.lora_b || p.ln_stats || p.geglu || p.stats_out || p.out_f32)) return false;
     if (mt == 4 && conv) return false;  // (tile id 10 is instantiated for bf16 GEMMs: gemm.hip keeps float32 launches off it)
     if (p.ksplit > 1 || !p.vec_ok || p.N % 16) return false;  // (the epilogue instances of this loop are the vectorised ones)
     if (p.lora_b && (conv || p.lora_groups != 1 || p.nseg != 1 || p.out_t || (p.lora_r != 32 && p.lora_r != 64 && p.lora_r != 128) || !p.lora_t || !p.lora_flags || !p.lora_epoch)) return false;  // in-launch LoRA here: one column group of a plain GEMM

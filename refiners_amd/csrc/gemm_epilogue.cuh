@@ -71,8 +71,11 @@ MI_DEV void ln_rowstat(const GemmP& p, int m0, int tid_all, float* rowstat) {
 // split: this workgroup's split-K index.
 // TR_ONLY: instantiate the transposed-tile path alone (the caller passes tr = true; block shapes the row-major path has no code for).
 // FAST: dispatch the row loop to the instance compiled for this launch's kind of epilogue (see EPIF).
-template <typename T, int MT, int NT, int BM, bool CONV, bool TR_ONLY = false, bool FAST = false>
-// colvec (LDS, or null): the tile's per-column vectors staged by the caller, [0, BN): the bias as float32 or the folded LayerNorm's s, [BN, 2 BN): its c (BN = 256);
+// WNC / COFF: the row-major path's lane g owns columns wn WNC + COFF + 4 NT g .. + 4 NT of the tile -- WNC = 16 NT, COFF = 0 unless a wave's columns are handed over
+// in two parts (the 80-column waves of the 8-wave loop: 4 blocks of 16 consecutive columns per lane, then one block of 4 per lane at COFF = 64).
+// CVN: the pitch of colvec (the tile's width).  ALLOW: the EPI_* parts this instance may run at all (the others are compiled out; the host keeps such launches off it).
+template <typename T, int MT, int NT, int BM, bool CONV, bool TR_ONLY = false, bool FAST = false, int WNC = 16 * NT, int COFF = 0, int CVN = 256, unsigned ALLOW = EPI_ALL>
+// colvec (LDS, or null): the tile's per-column vectors staged by the caller, [0, CVN): the bias as float32 or the folded LayerNorm's s, [CVN, 2 CVN): its c;
 // a workgroup that owns its CU alone reads them from there: a global load issued behind a row's stores waits for the stores (vmcnt is in order and counts them).
 MI_DEV void tile_epilogue(const GemmP& p, f32x4 (&acc)[MT][NT], const float* rowstat, int m0, int n0, int wm, int wn, int lane, bool tr, int split, const float* colvec = nullptr) {
     constexpr int WME = 16 * MT, WNE = 16 * NT;
@@ -102,7 +105,7 @@ MI_DEV void tile_epilogue(const GemmP& p, f32x4 (&acc)[MT][NT], const float* row
                     for (int r = 0; r < 4; ++r) v[4 * i + r] = acc[i][j][r];
                 if (p.ln_stats) {
                     float s, c;  // (two separate loads, not one load through a selected pointer: that would be a FLAT load, which waits on vmcnt)
-                    if (colvec) s = colvec[n - n0], c = colvec[256 + n - n0];
+                    if (colvec) s = colvec[n - n0], c = colvec[CVN + n - n0];
                     else s = p.ln_s[n], c = p.ln_c[n];
 #pragma unroll
                     for (int e = 0; e < RUN_T; ++e) {
@@ -138,7 +141,24 @@ MI_DEV void tile_epilogue(const GemmP& p, f32x4 (&acc)[MT][NT], const float* row
     if constexpr (!TR_ONLY) {
     // every lane owns RUN = 4*NT consecutive columns of MT rows
     constexpr int RUN = 4 * NT;
-    const int nl = wn * WNE + RUN * g;
+    static_assert(RUN % EPC == 0 || (RUN == 4 && EPC == 8), "a lane's run: whole 16-byte chunks, or 4 bf16 (8 bytes)");
+    constexpr int NCH = RUN % EPC == 0 ? RUN / EPC : 0;  // whole 16-byte chunks of a run
+    // RUN elements of T from p (16-byte loads, or one 8-byte load for a 4-element bf16 run) added to v
+    auto add_run = [&](float* v, const T* src) __attribute__((always_inline)) {
+        if constexpr (NCH > 0) {
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                Vec16<T> bv = load16<T>(src + c * EPC);
+#pragma unroll
+                for (int e = 0; e < EPC; ++e) v[c * EPC + e] += bv.get(e);
+            }
+        } else {
+            const bf16x4 bv = *reinterpret_cast<const bf16x4*>(src);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] += (float)bv[e];
+        }
+    };
+    const int nl = wn * WNC + COFF + RUN * g;
     const int n = n0 + nl;
     const bool full = p.vec_ok && (n + RUN <= p.N);
     if (p.ksplit > 1) {  // split-K: raw float32 partial sums; bias / residual / conversion happen in splitk_reduce_kernel
@@ -160,7 +180,7 @@ MI_DEV void tile_epilogue(const GemmP& p, f32x4 (&acc)[MT][NT], const float* row
         return;
     }
     auto rows = [&](auto fc) __attribute__((always_inline)) {
-    constexpr unsigned F = decltype(fc)::value;
+    constexpr unsigned F = decltype(fc)::value & ALLOW;
     float cs_a[RUN], cs_b[RUN];  // GemmP::colstats: the even row of the current 32-row block
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
@@ -184,7 +204,7 @@ MI_DEV void tile_epilogue(const GemmP& p, f32x4 (&acc)[MT][NT], const float* row
 #pragma unroll
                 for (int c = 0; c < RUN / 4; ++c) {
                     f32x4 sv, cv;
-                    if (colvec) sv = *reinterpret_cast<const f32x4*>(colvec + nl + 4 * c), cv = *reinterpret_cast<const f32x4*>(colvec + 256 + nl + 4 * c);
+                    if (colvec) sv = *reinterpret_cast<const f32x4*>(colvec + nl + 4 * c), cv = *reinterpret_cast<const f32x4*>(colvec + CVN + nl + 4 * c);
                     else sv = *reinterpret_cast<const f32x4*>(p.ln_s + n + 4 * c), cv = *reinterpret_cast<const f32x4*>(p.ln_c + n + 4 * c);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[4 * c + e] = rstd * (v[4 * c + e] - mean * sv[e]) + cv[e];
@@ -198,23 +218,10 @@ MI_DEV void tile_epilogue(const GemmP& p, f32x4 (&acc)[MT][NT], const float* row
                         for (int e = 0; e < 4; ++e) v[4 * c + e] += bv[e];
                     }
                 } else {
-#pragma unroll
-                    for (int c = 0; c < RUN / EPC; ++c) {
-                        Vec16<T> bv = load16<T>(bias + n + c * EPC);
-#pragma unroll
-                        for (int e = 0; e < EPC; ++e) v[c * EPC + e] += bv.get(e);
-                    }
+                    add_run(v, bias + n);
                 }
             }
-            if (EPIF(EPI_RB, rowbias) && mok) {
-                const T* rb = rowbias + (int64_t)(m / p.rows_per_group) * p.ld_rowbias + n;
-#pragma unroll
-                for (int c = 0; c < RUN / EPC; ++c) {
-                    Vec16<T> bv = load16<T>(rb + c * EPC);
-#pragma unroll
-                    for (int e = 0; e < EPC; ++e) v[c * EPC + e] += bv.get(e);
-                }
-            }
+            if (EPIF(EPI_RB, rowbias) && mok) add_run(v, rowbias + (int64_t)(m / p.rows_per_group) * p.ld_rowbias + n);
             if (EPIF(EPI_GELU, p.gelu)) {
 #pragma unroll
                 for (int e = 0; e < RUN; ++e) v[e] = epi_act(p.gelu, v[e]);
@@ -246,15 +253,7 @@ MI_DEV void tile_epilogue(const GemmP& p, f32x4 (&acc)[MT][NT], const float* row
                     }
                 }
             } else {
-                if (EPIF(EPI_RES, res) && mok) {
-                    const T* rp = res + (int64_t)m * p.ldres + n;
-#pragma unroll
-                    for (int c = 0; c < RUN / EPC; ++c) {
-                        Vec16<T> rv = load16<T>(rp + c * EPC);
-#pragma unroll
-                        for (int e = 0; e < EPC; ++e) v[c * EPC + e] += rv.get(e);
-                    }
-                }
+                if (EPIF(EPI_RES, res) && mok) add_run(v, res + (int64_t)m * p.ldres + n);
                 if (EPIF(EPI_F32, p.out_f32)) {
                     if (mok) {
                         float* of = reinterpret_cast<float*>(p.out) + (int64_t)m * p.ldo + n;
@@ -265,18 +264,30 @@ MI_DEV void tile_epilogue(const GemmP& p, f32x4 (&acc)[MT][NT], const float* row
                 }
                 T* op = out + (int64_t)m * p.ldo + n;
                 float rs = 0.f;  // sum of the values AS STORED (rounded to T): the next LayerNorm normalises the stored tensor
+                if constexpr (NCH > 0) {
 #pragma unroll
-                for (int c = 0; c < RUN / EPC; ++c) {
-                    Vec16<T> ov;
+                    for (int c = 0; c < NCH; ++c) {
+                        Vec16<T> ov;
 #pragma unroll
-                    for (int e = 0; e < EPC; ++e) ov.set(e, v[c * EPC + e]);
-                    if (mok) store16<T>(op + c * EPC, ov);
-                    if (EPIF(EPI_ST, p.stats_out) || EPIF(EPI_CS, p.colstats)) {
+                        for (int e = 0; e < EPC; ++e) ov.set(e, v[c * EPC + e]);
+                        if (mok) store16<T>(op + c * EPC, ov);
+                        if (EPIF(EPI_ST, p.stats_out) || EPIF(EPI_CS, p.colstats)) {
 #pragma unroll
-                        for (int e = 0; e < EPC; ++e) {
-                            v[c * EPC + e] = ov.get(e);
-                            rs += ov.get(e);
+                            for (int e = 0; e < EPC; ++e) {
+                                v[c * EPC + e] = ov.get(e);
+                                rs += ov.get(e);
+                            }
                         }
+                    }
+                } else {  // a 4-element bf16 run: one 8-byte store
+                    bf16x4 ov;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) ov[e] = (bf16_t)v[e];
+                    if (mok) *reinterpret_cast<bf16x4*>(op) = ov;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        v[e] = (float)ov[e];
+                        rs += v[e];
                     }
                 }
                 if (EPIF(EPI_CS, p.colstats)) {
@@ -294,9 +305,9 @@ MI_DEV void tile_epilogue(const GemmP& p, f32x4 (&acc)[MT][NT], const float* row
                             cs_a[e] += mok ? v[e] : 0.f;
                             cs_b[e] += mok ? v[e] * v[e] : 0.f;
                         }
-                        if constexpr (RUN == 8 || RUN == 16) colsum16<RUN>(cs_a, cs_b, c16);  // (other runs: probing tiles only, never launched with column statistics)
+                        if constexpr (RUN == 4 || RUN == 8 || RUN == 16) colsum16<RUN>(cs_a, cs_b, c16);  // (other runs: probing tiles only, never launched with column statistics)
                         const int blk = (m0 + wm * WME + 16 * (i - 1)) >> 5;  // (tiles start on multiples of 64 rows)
-                        if ((RUN == 16 || c16 < 8) && (blk << 5) < p.M) {
+                        if (c16 < RUN && (blk << 5) < p.M) {
                             f32x2 st = {cs_a[0], cs_b[0]};
                             *reinterpret_cast<f32x2*>(p.colstats + ((int64_t)blk * p.N + n + (c16 & (RUN - 1))) * 2) = st;
                         }

@@ -105,7 +105,8 @@ MI_DEV void stat_merge(float& n, float& mean, float& m2, float nb, float mb, flo
 
 // Column sums over the 16 lanes of a lane group (lane c16 = one row): a[e], b[e] hold this lane's contribution to column e of RUN; on return
 // lane c16 holds the 16-lane totals of column `c16 % RUN` in a[0], b[0].  Recursive halving: each exchange adds the partner's half and keeps
-// half of the columns (RUN = 8: one full exchange first, the two 8-lane halves then end with the same totals), 15 / 14 exchanges per
+// half of the columns (RUN = 8: one full exchange first, the two 8-lane halves then end with the same totals; RUN = 4: two full exchanges,
+// row_mirror and row_half_mirror, sum lanes c ^ {0, 7, 8, 15}, and the two quad steps then reach all 16), 15 / 14 exchanges per
 // quantity instead of 64 for an all-reduce, a fixed tree (deterministic).  The exchanges are DPP moves inside the 16-lane row (no LDS round
 // trip: __shfl_xor compiles to ds_bpermute): partner = row_mirror (15 - c), row_half_mirror (c ^ 7), quad_perm (c ^ 2), (c ^ 1) -- every
 // partner differs from the lane in exactly the bit that decides which half it keeps, and the four steps together reach all 16 lanes.
@@ -113,7 +114,7 @@ template <int CTRL> MI_DEV float dpp_f32(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
 template <int RUN> MI_DEV void colsum16(float (&a)[RUN], float (&b)[RUN], int c16) {
-    static_assert(RUN == 8 || RUN == 16, "8 or 16 columns per lane");
+    static_assert(RUN == 4 || RUN == 8 || RUN == 16, "4, 8 or 16 columns per lane");
     constexpr int ROW_MIRROR = 0x140, ROW_HALF_MIRROR = 0x141, QUAD_XOR2 = 0x4E, QUAD_XOR1 = 0xB1;
     auto step = [&](auto ctrl, int w) __attribute__((always_inline)) {  // w = the lane bit of this exchange = number of columns kept
         constexpr int CTRL = decltype(ctrl)::value;
@@ -128,16 +129,24 @@ template <int RUN> MI_DEV void colsum16(float (&a)[RUN], float (&b)[RUN], int c1
             }
         }
     };
-    if constexpr (RUN == 8) {
+    if constexpr (RUN == 16) {
+        step(std::integral_constant<int, ROW_MIRROR>{}, 8);
+    } else {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
+        for (int e = 0; e < RUN; ++e) {
             a[e] += dpp_f32<ROW_MIRROR>(a[e]);
             b[e] += dpp_f32<ROW_MIRROR>(b[e]);
         }
-    } else {
-        step(std::integral_constant<int, ROW_MIRROR>{}, 8);
     }
-    step(std::integral_constant<int, ROW_HALF_MIRROR>{}, 4);
+    if constexpr (RUN == 4) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            a[e] += dpp_f32<ROW_HALF_MIRROR>(a[e]);
+            b[e] += dpp_f32<ROW_HALF_MIRROR>(b[e]);
+        }
+    } else {
+        step(std::integral_constant<int, ROW_HALF_MIRROR>{}, 4);
+    }
     step(std::integral_constant<int, QUAD_XOR2>{}, 2);
     step(std::integral_constant<int, QUAD_XOR1>{}, 1);
 }

@@ -39,6 +39,8 @@ def candidates(a, only=None) -> list[tuple[int, int]]:
         out += [(7, 0), (8, 0)] + ([] if a.out_t else [(9, 0)])
     elif a.lora_b and not a.conv and a.lora_groups == 1 and a.nseg == 1 and not a.out_t:  # its in-launch LoRA: one column group of a plain GEMM, whole tiles
         out += [(7, 0), (9, 0)]
+    if a.dtype != 0 and not (a.lora_b or a.out_t or a.geglu == 1 or a.ln_stats or a.stats_out or a.out_f32):  # 12 = whole 128 x 320 tiles of the same loop
+        out.append((12, 0))
     if a.ksplit > 1:  # a launch the lowering split along K: only the 8-wave loop (which takes the whole K) is an alternative
         return [c for c in out if only is None or c[0] in only]
     for tile in (1, 2, 3, 4, 6):  # 128x128, 128x64, 64x128, 64x64 (4 waves); 6 = 128x128 with two K groups (8 waves)
@@ -134,7 +136,7 @@ def main() -> None:
         def apply(tile, st):
             for a in items:
                 a.tile, a.stages = tile, st
-                a.ksplit = 1 if tile in (7, 8, 9) else ks0
+                a.ksplit = 1 if tile in (7, 8, 9, 12) else ks0
                 if tile == 8:
                     native.attach_streamk(a, low._sk)
 

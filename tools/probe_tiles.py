@@ -25,7 +25,7 @@ def main():
               ("projx4", 8192, 1280, 1280, False), ("FF2x4", 8192, 5120, 1280, False), ("640x4", 32768, 640, 640, False)]  # (N = 1280 at 4 images: 160 tiles of 256 rows, 215 of 192)
     if "--n1280" in sys.argv:
         shapes = shapes[-3:] + [s_ for s_ in shapes if s_[0] in ("FF1x4", "4096^3")]
-    tiles = [(0, 0), (1, 2), (4, 2), (7, 0), (8, 0), (9, 0)]
+    tiles = [(0, 0), (1, 2), (4, 2), (7, 0), (8, 0), (9, 0), (12, 0)]
     for name, M, K, N, geglu in shapes:
         sets = []
         for _ in range(6):
@@ -36,7 +36,7 @@ def main():
         res = {t: [] for t in tiles}
         for rnd in range(3):
             for t in tiles:
-                if geglu and t[0] in (2, 4):
+                if geglu and t[0] in (2, 4, 12):
                     continue
                 try:
                     for x, w, o in sets:
