@@ -517,6 +517,62 @@ typedef struct mi355x_sam_postprocess_args {
 } mi355x_sam_postprocess_args;
 int mi355x_sam_postprocess_masks(const mi355x_sam_postprocess_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * StyleAligned shared self-attention (refiners_amd/csrc/style_aligned.hip).  Replaces what StyleAlignedAdapter inserts between the
+ * Q / K / V projections and ScaledDotProductAttention of every fl.SelfAttention
+ * (src/refiners/foundationals/latent_diffusion/style_aligned.py:15-282: ExtractReferenceFeatures, AdaIN, ScaleReferenceFeatures,
+ * Concatenate(dim=-2)).  A batch of B rows is made of B / n groups of n rows; the reference row of row b is r(b) = (b / n) * n.
+ * Attention itself is the unchanged mi355x_attention / mi355x_attention_general, called with Lq = L and Lk = 2 L on the packed buffers.
+ *
+ * mi355x_adain_stats -- per (sample, channel) mean and UNBIASED standard deviation (divide by L - 1, torch.std's default) over the L
+ * tokens of x [B][L][ldx] (+ b * x_batch_stride; C contiguous channels per row, C * element size a multiple of 16; x may be a column
+ * slice of a wider buffer).  stats: float32 [B][C][2] = (mean, std).  The tokens are cut into slabs; every slab carries
+ * (count, mean, M2) of its rows (Welford updates in float32) and the slabs are merged with Chan's formula in slab order: no sum of
+ * squares, no float atomics, replays are bit-equal.  ws: float32 scratch of ws_floats >= the value the _ws_floats query returns for
+ * (B, L, C).  L < 2 (no unbiased estimate) returns MI355X_ESHAPE. */
+typedef struct mi355x_adain_stats_args {
+    int32_t dtype;
+    int32_t B, L, C;
+    const void* x;
+    int64_t ldx, x_batch_stride;
+    float* stats;
+    float* ws;
+    int64_t ws_floats;
+} mi355x_adain_stats_args;
+int64_t mi355x_adain_stats_ws_floats(int32_t B, int32_t L, int32_t C);
+int mi355x_adain_stats(const mi355x_adain_stats_args* a, void* stream);
+
+/* mi355x_style_aligned_pack -- with s_b = 1 where b == r(b) and *scale (a float in DEVICE memory: the adapter's live scale, read at
+ * run time so that a captured graph follows it) elsewhere, and AdaIN(t)_b = (t - mean_b) / (std_b + eps) * std_r(b) + mean_r(b) per channel:
+ *   q    [B][L][ldq]      <- AdaIN(q), in place                                   (statistics: q_stats)
+ *   k_sh [B][Lkp][ld_ksh] :  rows [0, L) = AdaIN(k_b) (k_stats), rows [L, 2 L) = s_b * k_r(b) (the RAW projected keys)
+ *   vt_sh[C][B][Lkp]      :  columns [0, L) = vt[c][b][:], columns [L, 2 L) = s_b * vt[c][r(b)][:]    (vt: V^T [C][B][Lp])
+ * q_stats / k_stats: float32 (mean, std) pairs as mi355x_adain_stats writes them, sample b at + b * stats_batch_stride floats (so
+ * both may point into one [B][2 C][2] table computed over a packed Q|K buffer).  Lkp >= 2 L is the caller's padding (2 L rounded up
+ * to 64 for the attention kernels); rows / columns [2 L, Lkp) are never written: the caller zeroes them once.  Arithmetic in float32,
+ * one rounding at the store.  k and k_sh, vt and vt_sh must not overlap (MI355X_EARG).  Rows are moved as 16-byte vectors; V^T rows whose length or
+ * strides are not a multiple of 16 bytes take an element-wise path.  B % n != 0 returns MI355X_ESHAPE.  Two launches (Q / K rows, V^T rows). */
+typedef struct mi355x_style_aligned_args {
+    int32_t dtype;
+    int32_t B, L, C, n;
+    void* q;
+    int64_t ldq, q_batch_stride;
+    const void* k;
+    int64_t ldk, k_batch_stride;
+    const void* vt;
+    int64_t ldvt, vt_batch_stride;
+    const float* q_stats;
+    const float* k_stats;
+    int64_t stats_batch_stride;
+    const float* scale;
+    float eps;
+    void* k_sh;
+    int64_t ld_ksh, ksh_batch_stride;
+    void* vt_sh;
+    int64_t ld_vtsh, vtsh_batch_stride;
+} mi355x_style_aligned_args;
+int mi355x_style_aligned_pack(const mi355x_style_aligned_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ def namespace():
     from .fluxion import layers as fl
     from .fluxion.adapters import Conv2dLora, LinearLora, LoraAdapter
     from .latent_diffusion.adapters import ConditionEncoder, ControlLoraAdapter, SDXLIPAdapter, ZeroConvolution
+    from .latent_diffusion.style_aligned import StyleAlignedAdapter
 
     return SimpleNamespace(fl=fl, LinearLora=LinearLora, Conv2dLora=Conv2dLora, LoraAdapter=LoraAdapter, SDXLIPAdapter=SDXLIPAdapter,
-                           ControlLoraAdapter=ControlLoraAdapter, ConditionEncoder=ConditionEncoder, ZeroConvolution=ZeroConvolution)
+                           ControlLoraAdapter=ControlLoraAdapter, ConditionEncoder=ConditionEncoder, ZeroConvolution=ZeroConvolution, StyleAlignedAdapter=StyleAlignedAdapter)

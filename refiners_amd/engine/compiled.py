@@ -18,7 +18,8 @@ reference's own convention for unknown children -- the stock child loop runs (fl
 "unsupported => fall back, never error") -- at two levels, both reported: a context-free sub-tree inside a UNet stage runs through its own
 torch forward inside the recorded program (`.stats["fallback_nodes"]`); anything else (a node that needs the Chain's context store at run
 time, an unknown top-level layout) makes the WHOLE call run `unet(x)`, with a `RuntimeWarning` naming the reason and
-`.stats["whole_fallback"]` set.  Adapters outside SURVEY.md section 8 (FreeU, reference-only, StyleAligned ...) therefore keep working, unfused.
+`.stats["whole_fallback"]` set.  Adapters outside SURVEY.md section 8 (FreeU, reference-only ...) therefore keep working, unfused.
+StyleAlignedAdapter is lowered (`.stats["style_aligned_sites"]`): its scale lives in device memory and is refreshed before every replay.
 """
 from __future__ import annotations
 
@@ -100,6 +101,10 @@ class CompiledUNet:
         self.io: Optional[UNetIO] = None
         self.key: Any = None
         self.bad_key: Any = None  # the (tree state, geometry) key whose lowering raised Unsupported: those calls run the stock forward
+        # StyleAligned's ScaleReferenceFeatures of the tree as the last lowering met them, and their scales when the tree was last refused: assigning a
+        # scale bumps no tree epoch (the lowered program reads it from device memory), so a refusal is retried when these values moved
+        self.style_watch: list = []
+        self.bad_scales: Any = None
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.prologue_key: Any = None
         self.prologue_refs: Any = None  # the staged source tensors themselves (see _ident)
@@ -165,6 +170,8 @@ class CompiledUNet:
             io.t2i[name] = [torch.empty(tuple(f.shape), device=dev, dtype=dtype) for f in feats]
         low = UNetLowering(dev, dtype, self.cache, self.lora_mode)
         low.sag_capture = getattr(self, "sag_capture", True)
+        low.style_half_batch = self.io_override is not None  # StyleAligned: this program is ONE half of the CFG pair, all its rows share row 0
+        self.style_watch = low.style_modules  # (filled while lowering; kept when it raises Unsupported)
         low.lower(self.unet, io)
         self.cache.sweep()
         # the step program is replayed step after step: let every GEMM / conv pull the weights of the launches behind it into
@@ -245,7 +252,9 @@ class CompiledUNet:
         key = (self._tree_state(), tuple(x_shape), self.unet.dtype, None if got.get("timesteps_all") is None else int(got["timesteps_all"].numel()),
                tuple((k, tuple(v.shape)) for k, v in got["tokens"].items()),
                tuple((k, tuple(v.shape)) for k, v in got["conditions"].items()), got["pooled"] is not None,
-               tuple((k, tuple(tuple(f.shape) for f in feats)) for k, feats in got.get("t2i", {}).items()))
+               tuple((k, tuple(tuple(f.shape) for f in feats)) for k, feats in got.get("t2i", {}).items()), self.io_override is not None)
+        if key == self.bad_key and self.bad_scales != self._style_scales():
+            self.bad_key = None  # a StyleAligned scale was assigned since the refusal: look at the tree again
         if key != self.key:
             if key == self.bad_key:
                 raise Unsupported(self.stats.get("whole_fallback", "this tree could not be lowered"))
@@ -253,12 +262,39 @@ class CompiledUNet:
                 self._build(x_shape, device, got)
             except Unsupported as exc:
                 # remembered per (tree state, geometry): the next call does not walk the tree again; any inject / eject / scale change retries
+                # (StyleAligned scales bump no epoch: they are compared by value, see bad_scales)
                 self.bad_key, self.key, self.low, self.io, self.graph = key, None, None, None, None
+                self.bad_scales = self._style_scales()
                 self.stats = {"whole_fallback": str(exc), "fallback_nodes": ["<whole UNet>"], "step_ops": 0, "prologue_ops": 0}
                 warnings.warn(f"refiners_amd: this UNet tree is not lowered to the MI355X kernels ({exc}); running the stock Chain forward instead", RuntimeWarning, stacklevel=3)
                 raise
             self.key, self.bad_key = key, None
+        self._refresh_style_scale(key)
         return self._stage_inputs(got)
+
+    def _style_scales(self) -> tuple:
+        return tuple(float(m.scale) for m in self.style_watch)
+
+    def _refresh_style_scale(self, key: Any) -> None:
+        """StyleAligned's scale is a live attribute of the tree and the step is a captured graph: the kernels read it from one float in device
+        memory, rewritten here (on the replaying stream, in front of the replay) whenever the tree's value moved.  The lowered pattern has ONE
+        scale; a tree whose ScaleReferenceFeatures were set apart by hand is no longer that pattern and is refused like any other tree the
+        lowering does not know (stock forward behind the warning, retried once the scales change again)."""
+        low = self.low
+        if low is None or not low.style_modules:
+            return
+        vals = set(self._style_scales())
+        if len(vals) != 1:
+            why = "the StyleAligned layers carry different scales"
+            self.bad_key, self.key, self.low, self.io, self.graph = key, None, None, None, None
+            self.bad_scales = self._style_scales()
+            self.stats = {"whole_fallback": why, "fallback_nodes": ["<whole UNet>"], "step_ops": 0, "prologue_ops": 0}
+            warnings.warn(f"refiners_amd: this UNet tree is not lowered to the MI355X kernels ({why}); running the stock Chain forward instead", RuntimeWarning, stacklevel=4)
+            raise Unsupported(why)
+        v = vals.pop()
+        if v != low.style_scale_value:
+            low.style_scale.fill_(v)
+            low.style_scale_value = v
 
     def run_prologue(self) -> None:
         assert self.low is not None

@@ -77,7 +77,15 @@ class Lowering:
         self.prologue: list = []
         self.step: list = []
         self._target = self.step
-        self.stats = {"fallback_nodes": [], "lora_sites": 0, "ip_sites": 0}
+        self.stats = {"fallback_nodes": [], "lora_sites": 0, "ip_sites": 0, "style_aligned_sites": 0}
+        # StyleAligned shared self-attention (BlockLowering.shared_attention): whether this program is ONE half of the CFG pair (set by the engine),
+        # every ScaleReferenceFeatures met (collected before any check, so that the engine can watch their scales even when the lowering refuses),
+        # the one float of device memory the kernels read the scale from with the value it holds, and scratch shared by the sites (stream order)
+        self.style_half_batch = False
+        self.style_modules: list[Any] = []
+        self.style_scale: Optional[Tensor] = None
+        self.style_scale_value: Optional[float] = None
+        self._style_bufs: dict[Any, Any] = {}
 
     # -- recording targets ---------------------------------------------------------------------------------
     class _Section:

@@ -20,12 +20,13 @@ from .packing import Act, CatAct, ConvSpec, LinSpec, LoraPack, PackCache, Pool, 
 
 
 class BlockLowering(Lowering):
-    def _split_attention(self, att: Any, allow_causal: bool = False) -> tuple[list[Any], Any, Any, Optional[Any]]:
-        """Attention | SelfAttention | CrossAttentionAdapter(Attention) -> ([q, k, v nodes], sdpa-like, out node, ip)."""
+    def _split_attention(self, att: Any, allow_causal: bool = False, skip: Any = None) -> tuple[list[Any], Any, Any, Optional[Any]]:
+        """Attention | SelfAttention | CrossAttentionAdapter(Attention) -> ([q, k, v nodes], sdpa-like, out node, ip).
+        `skip`: a child the caller has taken care of (the StyleAligned Distribute, see _style_aligned)."""
         if isa(att, "CrossAttentionAdapter"):
             att = kids(att)[0]
         _expect(isa(att, "Attention"), f"expected an Attention chain, got {cname(att)}")
-        ch = [c for c in kids(att) if not isa(c, "SelfAttentionMap")]  # the SAG tap (handled by self_attention) stores probabilities, changes nothing
+        ch = [c for c in kids(att) if not isa(c, "SelfAttentionMap") and c is not skip]  # the SAG tap (handled by self_attention) stores probabilities, changes nothing
         if isa(att, "SelfAttention"):
             _expect(len(ch) == 4 and isa(ch[0], "Parallel") and all(isa(c, "Identity") for c in kids(ch[0])), "unexpected SelfAttention layout")
             ch = ch[1:]
@@ -39,6 +40,99 @@ class BlockLowering(Lowering):
         _expect(isa(sd, "ScaledDotProductAttention") and (allow_causal or not sd.is_causal), "causal or unknown SDPA node")
         _expect(sd.num_heads == att.num_heads, "head count mismatch")
         return kids(ch[0]), sd, ch[2], ip
+
+    # -- StyleAligned shared self-attention (style_aligned.py:154-282) -------------------------------------------------------------
+    def _style_branch(self, node: Any) -> tuple[bool, bool, Any, Optional[float]]:
+        """StyleAligned chain -> (adain, concatenate, its ScaleReferenceFeatures, AdaIN epsilon); anything but the adapter's own layout is Unsupported."""
+        ch = kids(node)
+        _expect(isa(node, "StyleAligned") and len(ch) in (3, 4), f"unexpected {cname(node)} among the StyleAligned layers")
+        adain = isa(ch[1], "AdaIN")
+        par, dist, last = ch[0], ch[-2], ch[-1]
+        _expect(len(ch) == (4 if adain else 3), "unexpected StyleAligned layout")
+        pc, dc = kids(par), kids(dist)
+        _expect(isa(par, "Parallel") and len(pc) == 2 and isa(pc[0], "Identity") and isa(pc[1], "ExtractReferenceFeatures"), "unexpected StyleAligned reference extraction")
+        _expect(isa(dist, "Distribute") and len(dc) == 2 and isa(dc[0], "Identity") and isa(dc[1], "ScaleReferenceFeatures"), "unexpected StyleAligned reference scaling")
+        concat = isa(last, "Concatenate")
+        if concat:
+            cc = kids(last)
+            _expect(last.dim == -2 and len(cc) == 2 and all(isa(c, "GetArg") for c in cc) and [c.index for c in cc] == [0, 1], "StyleAligned concatenates something else than (targets, reference) along the tokens")
+        else:
+            _expect(isa(last, "GetArg") and last.index == 0, "unexpected StyleAligned output selection")
+        return adain, concat, dc[1], float(ch[1].epsilon) if adain else None
+
+    def _style_aligned(self, att: Any) -> tuple[Any, Any, Optional[tuple[list[Any], float]]]:
+        """SelfAttention | SharedSelfAttentionAdapter(SelfAttention with Distribute(StyleAligned x 3) in front of its SDPA)
+        -> (the SelfAttention, the inserted Distribute or None, ([the three ScaleReferenceFeatures], AdaIN epsilon) or None).
+        Only the adapter's own pattern is taken: Q = AdaIN, K = AdaIN + concatenate, V = concatenate, one common scale."""
+        if not isa(att, "SharedSelfAttentionAdapter"):
+            return att, None, None
+        _expect(len(kids(att)) == 1 and isa(kids(att)[0], "SelfAttention"), "SharedSelfAttentionAdapter around something else than a SelfAttention")
+        att = kids(att)[0]
+        dist = [c for c in kids(att) if isa(c, "Distribute") and any(isa(b, "StyleAligned") for b in kids(c))]
+        _expect(len(dist) == 1 and len(kids(dist[0])) == 3, "SharedSelfAttentionAdapter without its three StyleAligned layers")
+        ch = [c for c in kids(att) if not isa(c, "SelfAttentionMap")]
+        _expect(len(ch) == 5 and ch[2] is dist[0] and isa(ch[3], "ScaledDotProductAttention"), "the StyleAligned layers are not between the projections and the attention")
+        branches = [self._style_branch(b) for b in kids(dist[0])]
+        _expect([(a, c) for a, c, _m, _e in branches] == [(True, False), (True, True), (False, True)],
+                "StyleAligned branches differ from (Q: AdaIN; K: AdaIN + concatenate; V: concatenate)")
+        mods = [m for _a, _c, m, _e in branches]
+        self.style_modules.extend(mods)
+        _expect(len({float(m.scale) for m in mods}) == 1, "the StyleAligned branches of one attention carry different scales")
+        _expect(branches[0][3] == branches[1][3], "the AdaIN layers of one attention carry different epsilons")
+        return att, dist[0], (mods, float(branches[0][3]))
+
+    def shared_attention(self, q: Tensor, k: Tensor, vt: Tensor, qk: Optional[Tensor], B: int, L: int, heads: int, shared: tuple[list[Any], float]) -> Tensor:
+        """SDPA(AdaIN(Q), [AdaIN(K) ; s K_ref], [V ; s V_ref]): token statistics of Q and K (one launch over the packed Q|K buffer where there is
+        one), the apply-and-pack launch, then the ordinary attention kernel over 2L keys.  The scale lives in device memory (`style_scale`,
+        refreshed by the engine before every replay), the reference-group size comes from the engine (`style_half_batch`)."""
+        mods, eps = shared
+        C = q.shape[1]
+        if self.style_half_batch:
+            n = B  # one half of the classifier-free-guidance pair per program (CompiledSDXL cfg_split): every row refers to row 0
+        else:
+            _expect(B % 2 == 0, f"StyleAligned splits the batch into two classifier-free-guidance halves: an odd batch ({B}) has none")
+            n = B // 2
+        if self.style_scale is None:
+            self.style_scale_value = float(mods[0].scale)
+            self.style_scale = torch.full((1,), self.style_scale_value, device=self.device, dtype=torch.float32)
+        _expect(float(mods[0].scale) == self.style_scale_value, "StyleAligned layers with different scales in one UNet")
+        bufs = self._style_bufs
+        view3 = lambda t, rows: t.as_strided((B, rows, C), (rows * t.stride(0), t.stride(0), 1))  # noqa: E731
+        q3, k3 = view3(q, L), view3(k, L)
+        lp = vt.shape[1] // B
+        vt3 = vt.as_strided((C, B, lp), (vt.stride(0), lp, 1))
+        packed = qk is not None and qk.is_contiguous() and qk.shape[1] == 2 * C
+        width = 2 * C if packed else C
+        need = native.adain_stats_ws_floats(B, L, width)
+        ws = bufs.get("ws")
+        if need and (ws is None or ws.numel() < need):
+            ws = bufs["ws"] = torch.empty(need, device=self.device, dtype=torch.float32)
+        if packed:
+            if ("stats", B, width) not in bufs:
+                bufs[("stats", B, width)] = torch.empty(B, width, 2, device=self.device, dtype=torch.float32)
+            st = bufs[("stats", B, width)]
+            native.adain_stats(qk.view(B, L, width), st, ws)
+            sq, sk = st[:, :C], st[:, C:]
+        else:
+            if ("stats2", B, C) not in bufs:
+                bufs[("stats2", B, C)] = torch.empty(2, B, C, 2, device=self.device, dtype=torch.float32)
+            st = bufs[("stats2", B, C)]
+            sq, sk = native.adain_stats(q3, st[0], ws), native.adain_stats(k3, st[1], ws)
+        lkp = self._pad_keys(2 * L)
+        pooled = lkp == 2 * L
+        if pooled:
+            ksh, vtsh = self.pool.get(B * lkp, C), self.pool.get(C, B * lkp)
+        else:  # the padding keys / columns are zeroed ONCE here (see _project_vt); sites of one shape share the pair (stream order)
+            if ("kv", B, lkp, C) not in bufs:
+                bufs[("kv", B, lkp, C)] = (torch.zeros(B * lkp, C, device=self.device, dtype=self.dtype), torch.zeros(C, B * lkp, device=self.device, dtype=self.dtype))
+            ksh, vtsh = bufs[("kv", B, lkp, C)]
+        native.style_aligned_pack(q3, k3, vt3, sq, sk, n, self.style_scale, eps, ksh.view(B, lkp, C), vtsh.view(C, B, lkp))
+        o = self.sdpa(q, B, heads, [(ksh, vtsh, 2 * L, 1.0)])
+        if pooled:
+            self.pool.put(ksh)
+            self.pool.put(vtsh)
+        self.stats["style_aligned_sites"] = self.stats.get("style_aligned_sites", 0) + 1
+        return o
 
     def sdpa(self, q: Tensor, B: int, heads: int, streams: list[tuple[Tensor, Tensor, int, float]], v_plain: Optional[list[Tensor]] = None) -> Tensor:
         """q: [B*Lq, C]; streams: (k [B*Lkp, C], vt [C, B*Lkp], Lk, out_scale) with Lkp = rows per sample."""
@@ -158,13 +252,17 @@ class BlockLowering(Lowering):
         """x += Wo SDPA(Wq h, Wk h, Wv h), h = LN(x)   (cross_attention.py:44-49; attentions.py:319-385).
         `stats`: row statistics of x (LayerNorm then runs inside the projection launches); `stats_out`: buffer for the
         statistics of the updated x."""
-        (qn, kn, vn), sd, on, ip = self._split_attention(att)
+        att, inserted, shared = self._style_aligned(att)
+        (qn, kn, vn), sd, on, ip = self._split_attention(att, skip=inserted)
         _expect(ip is None, "image cross-attention on a self-attention")
+        tap = next((c for c in kids(att) if isa(c, "SelfAttentionMap")), None)
+        _expect(shared is None or tap is None, "Self-Attention Guidance taps a StyleAligned shared self-attention: the two together are not lowered")
         heads = sd.num_heads
         qs, ks, vs = self.linear_spec(qn), self.linear_spec(kn), self.linear_spec(vn)
         _expect(qs.b is None and ks.b is None and vs.b is None, "q/k/v bias not supported")
         M, C = x.shape
         native_path = self.head_kernel(C // heads) is not None
+        _expect(shared is None or native_path, f"StyleAligned on heads of {C // heads} channels, which no flash kernel serves")
         L = M // B
         fold = self.ln_fusable(stats, qs, ks, vs)
         lnarg = (stats, ln) if fold else None
@@ -214,10 +312,13 @@ class BlockLowering(Lowering):
                     native.gemm([(h, self.kblocked(wl))], None, out_t=vt, nt_begin=0, ln=(stats, ls, lc, float(ln.eps)))
                 else:
                     vt = self._project_vt(h, vs, B, L, C)
-        tap = next((c for c in kids(att) if isa(c, "SelfAttentionMap")), None)
         if tap is not None and getattr(self, "sag_capture", True):
             self.sag_attention_mass(q, k, B, heads, L, C)
-        if native_path:
+        if shared is not None:
+            o = self.shared_attention(q, k, vt, qk, B, L, heads, shared)
+            if L % 64 == 0:
+                self.pool.put(vt)
+        elif native_path:
             o = self.sdpa(q, B, heads, [(k, vt, L, 1.0)])
             if L % 64 == 0:
                 self.pool.put(vt)
@@ -405,7 +506,7 @@ class BlockLowering(Lowering):
         """Run an unrecognised sub-tree through its own torch forward on an NCHW copy: the node-level half of the section 8(b) error convention
         ("unsupported => fall back to the stock child loop, never error", fluxion/layers/chain.py:226-243).  Only for sub-trees that do not touch
         the context store: at run time the Chain's contexts do not hold this program's tensors (residual slots, embeddings live in the lowered
-        program), so a node that reads or writes them -- FreeU's concatenator, reference-only / StyleAligned attention injections -- makes the WHOLE
+        program), so a node that reads or writes them -- FreeU's concatenator, reference-only attention injections -- makes the WHOLE
         tree fall back to the stock forward instead (Unsupported -> CompiledUNet.__call__).  The output geometry is whatever the node
         produces on a zero image of the input's shape (one trial call at lowering time)."""
         ctx_nodes = sorted({cname(s) for s in node.modules() if isa(s, "UseContext", "SetContext")})

@@ -284,6 +284,27 @@ class SamPostprocessArgs(C.Structure):
         ("binarize", C.c_int32), ("threshold", C.c_float),
     ]
 
+
+class AdainStatsArgs(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int32), ("B", C.c_int32), ("L", C.c_int32), ("C", C.c_int32),
+        ("x", C.c_void_p), ("ldx", C.c_int64), ("x_batch_stride", C.c_int64),
+        ("stats", C.c_void_p), ("ws", C.c_void_p), ("ws_floats", C.c_int64),
+    ]
+
+
+class StyleAlignedArgs(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int32), ("B", C.c_int32), ("L", C.c_int32), ("C", C.c_int32), ("n", C.c_int32),
+        ("q", C.c_void_p), ("ldq", C.c_int64), ("q_batch_stride", C.c_int64),
+        ("k", C.c_void_p), ("ldk", C.c_int64), ("k_batch_stride", C.c_int64),
+        ("vt", C.c_void_p), ("ldvt", C.c_int64), ("vt_batch_stride", C.c_int64),
+        ("q_stats", C.c_void_p), ("k_stats", C.c_void_p), ("stats_batch_stride", C.c_int64),
+        ("scale", C.c_void_p), ("eps", C.c_float),
+        ("k_sh", C.c_void_p), ("ld_ksh", C.c_int64), ("ksh_batch_stride", C.c_int64),
+        ("vt_sh", C.c_void_p), ("ld_vtsh", C.c_int64), ("vtsh_batch_stride", C.c_int64),
+    ]
+
 #: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "mi355x_abi_version",
@@ -315,6 +336,9 @@ EXPORTS = [
     "mi355x_convt2x2_ln_gelu",
     "mi355x_sam_mask_head",
     "mi355x_sam_postprocess_masks",
+    "mi355x_adain_stats_ws_floats",
+    "mi355x_adain_stats",
+    "mi355x_style_aligned_pack",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -370,6 +394,10 @@ def load(path: Optional[Path] = None) -> C.CDLL:
                                             C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
     lib.mi355x_sam_mask_head.argtypes = [C.POINTER(SamMaskHeadArgs), C.c_void_p]
     lib.mi355x_sam_postprocess_masks.argtypes = [C.POINTER(SamPostprocessArgs), C.c_void_p]
+    lib.mi355x_adain_stats_ws_floats.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.mi355x_adain_stats_ws_floats.restype = C.c_int64
+    lib.mi355x_adain_stats.argtypes = [C.POINTER(AdainStatsArgs), C.c_void_p]
+    lib.mi355x_style_aligned_pack.argtypes = [C.POINTER(StyleAlignedArgs), C.c_void_p]
     lib.mi355x_set_option.argtypes = [C.c_char_p, C.c_int]
     lib.mi355x_attention_set_glds.argtypes = [C.c_int]
     lib.mi355x_attention_general_set_fast.argtypes = [C.c_int]
@@ -1319,6 +1347,54 @@ def sam_postprocess_masks(low: Tensor, R: int, scaled: tuple[int, int], out: Ten
         a.binarize, a.threshold = 1, float(threshold)
     _launch("mi355x_sam_postprocess_masks", (C.byref(a),), "mi355x_sam_postprocess_masks")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ StyleAligned shared self-attention (csrc/style_aligned.hip)
+def adain_stats_ws_floats(B: int, L: int, C_: int) -> int:
+    """Floats of the scratch mi355x_adain_stats needs for [B, L, C_] (0 when one slab of tokens per workgroup column is enough)."""
+    return int(load().mi355x_adain_stats_ws_floats(B, L, C_))
+
+
+def adain_stats(x: Tensor, stats: Tensor, ws: Optional[Tensor] = None) -> Tensor:
+    """x [B, L, C] view (contiguous channels; may be a column slice of a wider buffer) -> stats float32 [B, C, 2] = (mean, unbiased std) over
+    the L tokens.  ws: float32 scratch of adain_stats_ws_floats(B, L, C) elements."""
+    assert x.dim() == 3 and x.stride(2) == 1 and stats.dtype == torch.float32 and stats.is_contiguous() and tuple(stats.shape) == (x.shape[0], x.shape[2], 2)
+    a = AdainStatsArgs()
+    a.dtype = dtype_code(x.dtype)
+    a.B, a.L, a.C = x.shape
+    a.x, a.ldx, a.x_batch_stride, a.stats = x.data_ptr(), x.stride(1), x.stride(0), stats.data_ptr()
+    need = adain_stats_ws_floats(a.B, a.L, a.C)
+    if need:
+        assert ws is not None and ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= need
+        a.ws, a.ws_floats = ws.data_ptr(), ws.numel()
+    _launch("mi355x_adain_stats", (C.byref(a),), "mi355x_adain_stats", keep=(ws, stats))
+    return stats
+
+
+def style_aligned_pack(q: Tensor, k: Tensor, vt: Tensor, q_stats: Tensor, k_stats: Tensor, group: int, scale: Tensor, eps: float, k_sh: Tensor, vt_sh: Tensor) -> None:
+    """q, k [B, L, C] views (q is rewritten in place), vt [C, B, Lp] view; q_stats / k_stats float32 [B, C, 2] views (batch stride free: column
+    halves of one [B, 2C, 2] table); group = rows per reference group; scale: one float32 on the device; k_sh [B, Lkp, C], vt_sh [C, B, Lkp],
+    Lkp >= 2L, padding zeroed by the caller.  See mi355x_style_aligned_pack in the header."""
+    B, L, C_ = q.shape
+    for t in (q, k, vt, k_sh, vt_sh):
+        assert t.dim() == 3 and t.stride(2) == 1 and t.dtype == q.dtype
+    assert tuple(k.shape) == (B, L, C_) and vt.shape[0] == C_ and vt.shape[1] == B and vt.shape[2] >= L
+    assert k_sh.shape[0] == B and k_sh.shape[1] >= 2 * L and k_sh.shape[2] == C_ and vt_sh.shape[0] == C_ and vt_sh.shape[1] == B and vt_sh.shape[2] >= 2 * L
+    for st in (q_stats, k_stats):
+        assert st.dtype == torch.float32 and tuple(st.shape) == (B, C_, 2) and st.stride(2) == 1 and st.stride(1) == 2
+    assert q_stats.stride(0) == k_stats.stride(0) and scale.dtype == torch.float32 and scale.numel() >= 1
+    a = StyleAlignedArgs()
+    a.dtype = dtype_code(q.dtype)
+    a.B, a.L, a.C, a.n = B, L, C_, group
+    a.q, a.ldq, a.q_batch_stride = q.data_ptr(), q.stride(1), q.stride(0)
+    a.k, a.ldk, a.k_batch_stride = k.data_ptr(), k.stride(1), k.stride(0)
+    a.vt, a.ldvt, a.vt_batch_stride = vt.data_ptr(), vt.stride(0), vt.stride(1)
+    a.q_stats, a.k_stats, a.stats_batch_stride = q_stats.data_ptr(), k_stats.data_ptr(), q_stats.stride(0)
+    a.scale, a.eps = scale.data_ptr(), eps
+    a.k_sh, a.ld_ksh, a.ksh_batch_stride = k_sh.data_ptr(), k_sh.stride(1), k_sh.stride(0)
+    a.vt_sh, a.ld_vtsh, a.vtsh_batch_stride = vt_sh.data_ptr(), vt_sh.stride(0), vt_sh.stride(1)
+    _launch("mi355x_style_aligned_pack", (C.byref(a),), "mi355x_style_aligned_pack", keep=(q_stats, k_stats, scale, k_sh, vt_sh))
+
 
 def set_glds(enabled: bool) -> None:
     """A/B switch: global_load_lds staging (default) vs register staging, for the GEMM and attention tile loaders."""
