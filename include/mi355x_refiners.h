@@ -573,6 +573,91 @@ typedef struct mi355x_style_aligned_args {
 } mi355x_style_aligned_args;
 int mi355x_style_aligned_pack(const mi355x_style_aligned_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * MultiDiffusion (refiners_amd/csrc/multi_diffusion.hip).  Replaces the torch ops MultiDiffusion.__call__ runs around diffuse_target
+ * (src/refiners/foundationals/latent_diffusion/multi_diffusion.py:98-123): crop / add_noise in front of the UNet, the solver call behind it
+ * with one solver and one condition_scale PER target (stable_diffusion_xl/multi_diffusion.py:20-33), paste / accumulate / divide on the
+ * canvas.  NCHW, contiguous, canvas batch 1.  Descriptor and coefficient tables are read from DEVICE memory so that a captured graph is
+ * replayed with new values; gather and blend also take a HOST copy of the same rows, which is what the call validates (a tile outside the
+ * canvas, a bad source kind or offset: negative code, nothing launched).  The kernels check the device rows again and move nothing for a
+ * row that left the contract since; an opacity-mask POINTER cannot be checked there and must stay the validated one.
+ * At most MI355X_MD_MAX_TARGETS targets per call.  No float atomics: replays are bit-equal. */
+#define MI355X_MD_MAX_TARGETS 64
+enum { MI355X_MD_SRC_CANVAS = 0, MI355X_MD_SRC_INIT = 1 };
+enum { MI355X_MD_FORM_DDIM = 0, MI355X_MD_FORM_LINEAR = 1 };
+
+/* mi355x_md_gather -- for T targets of one tile size h x w (multi_diffusion.py:103-114, model.py:139-141):
+ *   view[t]     = canvas[:, top : top + h, left : left + w]                            kind == MI355X_MD_SRC_CANVAS  (target.crop(x))
+ *               = a * init[init_row] + b * noise[:, top : top + h, left : left + w]    kind == MI355X_MD_SRC_INIT    (Solver.add_noise,
+ *                 solvers/solver.py:244-266, on the start step of a target with init_latents: two products and a sum, no fused multiply-add)
+ *   model_in[t] = model_in[T + t] = s * view[t]        (Solver.scale_model_input on cat(view, view); the STORED view is scaled)
+ * canvas, noise: [C][H][W]; init: [n_init][C][h][w] (NULL when no row uses it); view: [T][C][h][w]; model_in: [2T][C][h][w].  top, left and W are
+ * arbitrary: the source is read by element, the outputs are written as 4-element vectors when w % 4 == 0 and they are 16-byte aligned.
+ * view / model_in overlapping an input or each other: MI355X_EARG. */
+typedef struct mi355x_md_gather_desc {
+    int32_t kind, top, left, init_row;
+    float a, b, s;
+    int32_t reserved;
+} mi355x_md_gather_desc;
+typedef struct mi355x_md_gather_args {
+    int32_t dtype;
+    int32_t T, C, h, w, H, W, n_init;
+    const void* canvas;
+    const void* noise;
+    const void* init;
+    const mi355x_md_gather_desc* desc;      /* device, T rows */
+    const mi355x_md_gather_desc* desc_host; /* host copy, validated */
+    void* view;
+    void* model_in;
+} mi355x_md_gather_args;
+int mi355x_md_gather(const mi355x_md_gather_args* a, void* stream);
+
+/* mi355x_md_target_step -- classifier-free guidance + solver update of T targets, n elements each, target t with ITS row coef + 8 t (float32,
+ * device memory).  unet_out: [2T][n], the T unconditional outputs then the T conditional ones (model.py:142-145).
+ *   MI355X_MD_FORM_DDIM   row {cfg, sqrt(a_t), sqrt(1 - a_t), sqrt(a_prev), sqrt(1 - a_prev), -, -, -}: the arithmetic of mi355x_cfg_ddim_step
+ *   MI355X_MD_FORM_LINEAR row {cfg, hx, he, kx, ke, kd, kp, -}: the arithmetic of mi355x_cfg_linear_step, hist[t] read and replaced by d
+ * in the same operation order (at T = 1 the results are the same bits).  stepped[t] <- the updated view; stepped may be view itself, any
+ * other overlap of view / unet_out / stepped / hist returns MI355X_EARG.  No next-step model input is written: the next step gathers it
+ * from the blended canvas.  4-element vectors when n % 4 == 0 and every pointer is 16-byte aligned. */
+typedef struct mi355x_md_step_args {
+    int32_t dtype;
+    int32_t form, T;
+    int64_t n;
+    const void* view;
+    const void* unet_out;
+    void* stepped;
+    void* hist; /* MI355X_MD_FORM_LINEAR only */
+    const float* coef;
+} mi355x_md_step_args;
+int mi355x_md_target_step(const mi355x_md_step_args* a, void* stream);
+
+/* mi355x_md_blend -- the canvas update of multi_diffusion.py:116-123 in gather form.  For every canvas element (c, y, x), over the targets
+ * t = 0 .. n_targets - 1 IN ORDER whose tile holds (y, x):
+ *   wgt = mask ? weight * mask[c * mask_sc + (y - top) * mask_sh + (x - left) * mask_sw] : weight      (float32 mask, broadcast strides)
+ *   num += wgt;  cum += wgt * stepped[stepped_off + (c * h + y - top) * w + x - left]
+ * then canvas = num > 0 ? cum / num : canvas, in place, with a correctly rounded division.  Each sum is one product and one addition, each
+ * rounded once: in float32 the result is the reference's bits.  The walk in list order is the reference's summation order; one thread owns
+ * an element (or four of a row when W % 4 == 0), so nothing is accumulated across threads.  stepped: stepped_elems elements that hold
+ * every target's [C][h][w] tile at its offset; overlapping the canvas returns MI355X_EARG.  n_targets == 0 launches nothing. */
+typedef struct mi355x_md_blend_desc {
+    int32_t top, left, h, w;
+    float weight;
+    int32_t reserved;
+    int64_t stepped_off;
+    const float* mask; /* NULL: the target is fully opaque */
+    int64_t mask_sc, mask_sh, mask_sw;
+} mi355x_md_blend_desc;
+typedef struct mi355x_md_blend_args {
+    int32_t dtype;
+    int32_t n_targets, C, H, W;
+    void* canvas;
+    const void* stepped;
+    int64_t stepped_elems;
+    const mi355x_md_blend_desc* desc;      /* device, n_targets rows */
+    const mi355x_md_blend_desc* desc_host; /* host copy, validated */
+} mi355x_md_blend_args;
+int mi355x_md_blend(const mi355x_md_blend_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

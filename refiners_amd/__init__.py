@@ -8,7 +8,11 @@ def namespace():
     from .fluxion import layers as fl
     from .fluxion.adapters import Conv2dLora, LinearLora, LoraAdapter
     from .latent_diffusion.adapters import ConditionEncoder, ControlLoraAdapter, SDXLIPAdapter, ZeroConvolution
+    from .latent_diffusion.multi_diffusion import (DiffusionTarget, MultiDiffusion, SD1DiffusionTarget, SD1MultiDiffusion, SDXLMultiDiffusion, SDXLTarget, Size,
+                                                   Tile)
     from .latent_diffusion.style_aligned import StyleAlignedAdapter
 
     return SimpleNamespace(fl=fl, LinearLora=LinearLora, Conv2dLora=Conv2dLora, LoraAdapter=LoraAdapter, SDXLIPAdapter=SDXLIPAdapter,
-                           ControlLoraAdapter=ControlLoraAdapter, ConditionEncoder=ConditionEncoder, ZeroConvolution=ZeroConvolution, StyleAlignedAdapter=StyleAlignedAdapter)
+                           ControlLoraAdapter=ControlLoraAdapter, ConditionEncoder=ConditionEncoder, ZeroConvolution=ZeroConvolution, StyleAlignedAdapter=StyleAlignedAdapter,
+                           Tile=Tile, Size=Size, DiffusionTarget=DiffusionTarget, MultiDiffusion=MultiDiffusion, SDXLTarget=SDXLTarget,
+                           SDXLMultiDiffusion=SDXLMultiDiffusion, SD1DiffusionTarget=SD1DiffusionTarget, SD1MultiDiffusion=SD1MultiDiffusion)

@@ -13,7 +13,7 @@ from pathlib import Path
 
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = CSRC / "libmi355x_refiners.so"
-SOURCES = ["gemm.hip", "gemm_conv.hip", "gemm8.hip", "attention.hip", "attention_general.hip", "norm.hip", "elementwise.hip", "sam_decoder.hip", "style_aligned.hip"]
+SOURCES = ["gemm.hip", "gemm_conv.hip", "gemm8.hip", "attention.hip", "attention_general.hip", "norm.hip", "elementwise.hip", "sam_decoder.hip", "style_aligned.hip", "multi_diffusion.hip"]
 HEADERS = ["common.cuh", "gemm_params.cuh", "gemm_epilogue.cuh", "gemm_kernel.cuh", "gemm8_kernel.cuh", "gemm_lora_producer.cuh", "../../include/mi355x_refiners.h"]
 ARCH = "gfx950"
 #: headers each translation unit includes (an incremental build -- `python -m refiners_amd.build_native` without --force -- recompiles a source only when it or one of these changed)
@@ -22,7 +22,7 @@ DEPS = {
     "gemm_conv.hip": ["common.cuh", "gemm_params.cuh", "gemm_epilogue.cuh", "gemm_kernel.cuh", "gemm_lora_producer.cuh"],
     "gemm8.hip": ["common.cuh", "gemm_params.cuh", "gemm_epilogue.cuh", "gemm8_kernel.cuh", "gemm_lora_producer.cuh"],
     "attention.hip": ["common.cuh"], "attention_general.hip": ["common.cuh"], "norm.hip": ["common.cuh"], "elementwise.hip": ["common.cuh"],
-    "sam_decoder.hip": ["common.cuh"], "style_aligned.hip": ["common.cuh"],
+    "sam_decoder.hip": ["common.cuh"], "style_aligned.hip": ["common.cuh"], "multi_diffusion.hip": ["common.cuh"],
 }
 
 

@@ -305,6 +305,39 @@ class StyleAlignedArgs(C.Structure):
         ("vt_sh", C.c_void_p), ("ld_vtsh", C.c_int64), ("vtsh_batch_stride", C.c_int64),
     ]
 
+
+class MdGatherDesc(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("top", C.c_int32), ("left", C.c_int32), ("init_row", C.c_int32), ("a", C.c_float), ("b", C.c_float), ("s", C.c_float), ("reserved", C.c_int32)]
+
+
+class MdGatherArgs(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int32), ("T", C.c_int32), ("C", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_init", C.c_int32),
+        ("canvas", C.c_void_p), ("noise", C.c_void_p), ("init", C.c_void_p), ("desc", C.c_void_p), ("desc_host", C.c_void_p), ("view", C.c_void_p), ("model_in", C.c_void_p),
+    ]
+
+
+class MdStepArgs(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int32), ("form", C.c_int32), ("T", C.c_int32), ("n", C.c_int64),
+        ("view", C.c_void_p), ("unet_out", C.c_void_p), ("stepped", C.c_void_p), ("hist", C.c_void_p), ("coef", C.c_void_p),
+    ]
+
+
+class MdBlendDesc(C.Structure):
+    _fields_ = [
+        ("top", C.c_int32), ("left", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("weight", C.c_float), ("reserved", C.c_int32), ("stepped_off", C.c_int64),
+        ("mask", C.c_void_p), ("mask_sc", C.c_int64), ("mask_sh", C.c_int64), ("mask_sw", C.c_int64),
+    ]
+
+
+class MdBlendArgs(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int32), ("n_targets", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("canvas", C.c_void_p), ("stepped", C.c_void_p), ("stepped_elems", C.c_int64), ("desc", C.c_void_p), ("desc_host", C.c_void_p),
+    ]
+
+
 #: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "mi355x_abi_version",
@@ -339,6 +372,9 @@ EXPORTS = [
     "mi355x_adain_stats_ws_floats",
     "mi355x_adain_stats",
     "mi355x_style_aligned_pack",
+    "mi355x_md_gather",
+    "mi355x_md_target_step",
+    "mi355x_md_blend",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -398,6 +434,9 @@ def load(path: Optional[Path] = None) -> C.CDLL:
     lib.mi355x_adain_stats_ws_floats.restype = C.c_int64
     lib.mi355x_adain_stats.argtypes = [C.POINTER(AdainStatsArgs), C.c_void_p]
     lib.mi355x_style_aligned_pack.argtypes = [C.POINTER(StyleAlignedArgs), C.c_void_p]
+    lib.mi355x_md_gather.argtypes = [C.POINTER(MdGatherArgs), C.c_void_p]
+    lib.mi355x_md_target_step.argtypes = [C.POINTER(MdStepArgs), C.c_void_p]
+    lib.mi355x_md_blend.argtypes = [C.POINTER(MdBlendArgs), C.c_void_p]
     lib.mi355x_set_option.argtypes = [C.c_char_p, C.c_int]
     lib.mi355x_attention_set_glds.argtypes = [C.c_int]
     lib.mi355x_attention_general_set_fast.argtypes = [C.c_int]
@@ -1394,6 +1433,85 @@ def style_aligned_pack(q: Tensor, k: Tensor, vt: Tensor, q_stats: Tensor, k_stat
     a.k_sh, a.ld_ksh, a.ksh_batch_stride = k_sh.data_ptr(), k_sh.stride(1), k_sh.stride(0)
     a.vt_sh, a.ld_vtsh, a.vtsh_batch_stride = vt_sh.data_ptr(), vt_sh.stride(0), vt_sh.stride(1)
     _launch("mi355x_style_aligned_pack", (C.byref(a),), "mi355x_style_aligned_pack", keep=(q_stats, k_stats, scale, k_sh, vt_sh))
+
+
+# ------------------------------------------------------------------------------------------------ MultiDiffusion (csrc/multi_diffusion.hip)
+MD_MAX_TARGETS = 64
+MD_SRC_CANVAS, MD_SRC_INIT = 0, 1
+MD_GATHER_DESC_BYTES, MD_BLEND_DESC_BYTES = C.sizeof(MdGatherDesc), C.sizeof(MdBlendDesc)
+
+
+def _md_rows(arr, n: int, row_bytes: int) -> Tensor:
+    """A ctypes descriptor array as a uint8 CPU tensor [n, row_bytes]; no rows give an empty table (torch.frombuffer refuses an empty buffer)."""
+    if n == 0:
+        return torch.empty(0, row_bytes, dtype=torch.uint8)
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).view(n, row_bytes)
+
+
+def md_gather_rows(rows: list) -> Tensor:
+    """[(kind, top, left, init_row, a, b, s)] -> the descriptor rows of mi355x_md_gather as a uint8 CPU tensor [T, 32] (copy it to the device table)."""
+    arr = (MdGatherDesc * len(rows))()
+    for d, (kind, top, left, init_row, a, b, s) in zip(arr, rows):
+        d.kind, d.top, d.left, d.init_row, d.a, d.b, d.s = int(kind), int(top), int(left), int(init_row), float(a), float(b), float(s)
+    return _md_rows(arr, len(rows), MD_GATHER_DESC_BYTES)
+
+
+def md_blend_rows(rows: list) -> Tensor:
+    """[(top, left, h, w, weight, stepped_off, mask or None)] -> the descriptor rows of mi355x_md_blend as a uint8 CPU tensor [n, 64].  A mask is a float32
+    device tensor that broadcasts to [C, h, w] (or [1, C, h, w]): `.expand()` it first, its strides go into the row; keep it alive as long as the rows are used."""
+    arr = (MdBlendDesc * len(rows))()
+    for d, (top, left, h, w, weight, off, mask) in zip(arr, rows):
+        d.top, d.left, d.h, d.w, d.weight, d.stepped_off = int(top), int(left), int(h), int(w), float(weight), int(off)
+        if mask is not None:
+            assert mask.dtype == torch.float32 and mask.dim() in (3, 4) and tuple(mask.shape[-2:]) == (h, w) and (mask.dim() == 3 or mask.shape[0] == 1)
+            d.mask, (d.mask_sc, d.mask_sh, d.mask_sw) = mask.data_ptr(), mask.stride()[-3:]
+    return _md_rows(arr, len(rows), MD_BLEND_DESC_BYTES)
+
+
+def md_gather(canvas: Tensor, noise: Optional[Tensor], init: Optional[Tensor], desc: Tensor, desc_host: Tensor, view: Tensor, model_in: Tensor) -> None:
+    """canvas (noise) [1, C, H, W]; init [n_init, C, h, w] or None; desc: device uint8 [T, 32], desc_host: the same rows on the host (md_gather_rows);
+    view [T, C, h, w], model_in [2T, C, h, w].  See mi355x_md_gather in the header."""
+    T, C_, h, w = view.shape
+    assert canvas.dim() == 4 and canvas.shape[0] == 1 and canvas.shape[1] == C_ and tuple(model_in.shape) == (2 * T, C_, h, w)
+    for t in (canvas, noise, init, view, model_in):
+        assert t is None or (t.is_contiguous() and t.dtype == canvas.dtype)
+    assert noise is None or noise.shape == canvas.shape
+    assert init is None or tuple(init.shape[1:]) == (C_, h, w)
+    assert desc.dtype == torch.uint8 and desc.is_contiguous() and desc.numel() >= T * MD_GATHER_DESC_BYTES and desc.device == canvas.device
+    assert desc_host.dtype == torch.uint8 and desc_host.is_contiguous() and desc_host.numel() >= T * MD_GATHER_DESC_BYTES and desc_host.device.type == "cpu"
+    a = MdGatherArgs()
+    a.dtype = dtype_code(canvas.dtype)
+    a.T, a.C, a.h, a.w, a.H, a.W, a.n_init = T, C_, h, w, canvas.shape[2], canvas.shape[3], 0 if init is None else init.shape[0]
+    a.canvas, a.noise, a.init = canvas.data_ptr(), None if noise is None else noise.data_ptr(), None if init is None else init.data_ptr()
+    a.desc, a.desc_host, a.view, a.model_in = desc.data_ptr(), desc_host.data_ptr(), view.data_ptr(), model_in.data_ptr()
+    _launch("mi355x_md_gather", (C.byref(a),), "mi355x_md_gather", keep=(a, canvas, noise, init, desc, desc_host, view, model_in))
+
+
+def md_target_step(view: Tensor, unet_out: Tensor, stepped: Tensor, hist: Optional[Tensor], coef: Tensor, linear: bool) -> None:
+    """view, stepped (, hist) [T, ...]; unet_out [2T, ...] = (unconditional, conditional); coef: float32 [T, 8] on the device, one row per target:
+    (cfg, sqrt(a_t), sqrt(1 - a_t), sqrt(a_prev), noise factor, 0, 0, 0) or, `linear`, (cfg, hx, he, kx, ke, kd, kp, -).  See mi355x_md_target_step."""
+    T = view.shape[0]
+    for t in (view, unet_out, stepped, hist):
+        assert t is None or (t.is_contiguous() and t.dtype == view.dtype)
+    assert unet_out.numel() == 2 * view.numel() and stepped.shape == view.shape and (hist is None or hist.shape == view.shape)
+    assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.numel() >= 8 * T and coef.device == view.device
+    a = MdStepArgs()
+    a.dtype, a.form, a.T, a.n = dtype_code(view.dtype), 1 if linear else 0, T, view.numel() // T
+    a.view, a.unet_out, a.stepped, a.hist, a.coef = view.data_ptr(), unet_out.data_ptr(), stepped.data_ptr(), None if hist is None else hist.data_ptr(), coef.data_ptr()
+    _launch("mi355x_md_target_step", (C.byref(a),), "mi355x_md_target_step", keep=(a, view, unet_out, stepped, hist, coef))
+
+
+def md_blend(canvas: Tensor, stepped: Tensor, desc: Tensor, desc_host: Tensor, n_targets: int) -> Tensor:
+    """canvas [1, C, H, W], updated in place; stepped: any contiguous tensor of the canvas dtype that holds every target's [C, h, w] tile at its row's
+    offset; desc / desc_host: device / host uint8 rows of md_blend_rows.  See mi355x_md_blend in the header."""
+    assert canvas.dim() == 4 and canvas.shape[0] == 1 and canvas.is_contiguous() and stepped.is_contiguous() and stepped.dtype == canvas.dtype
+    assert desc.dtype == torch.uint8 and desc.is_contiguous() and desc.numel() >= n_targets * MD_BLEND_DESC_BYTES and desc.device == canvas.device
+    assert desc_host.dtype == torch.uint8 and desc_host.is_contiguous() and desc_host.numel() >= n_targets * MD_BLEND_DESC_BYTES and desc_host.device.type == "cpu"
+    a = MdBlendArgs()
+    a.dtype, a.n_targets, (a.C, a.H, a.W) = dtype_code(canvas.dtype), n_targets, canvas.shape[1:]
+    a.canvas, a.stepped, a.stepped_elems, a.desc, a.desc_host = canvas.data_ptr(), stepped.data_ptr(), stepped.numel(), desc.data_ptr(), desc_host.data_ptr()
+    _launch("mi355x_md_blend", (C.byref(a),), "mi355x_md_blend", keep=(a, canvas, stepped, desc, desc_host))
+    return canvas
 
 
 def set_glds(enabled: bool) -> None:
