@@ -658,6 +658,106 @@ typedef struct mi355x_md_blend_args {
 } mi355x_md_blend_args;
 int mi355x_md_blend(const mi355x_md_blend_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Tiled VAE (refiners_amd/csrc/norm.hip, tiled_vae.hip).  Replaces what LatentDiffusionAutoencoder.tiled_inference adds around encode / decode
+ * (src/refiners/foundationals/latent_diffusion/auto_encoder.py:209-621): FixedGroupNorm (GroupNorm with statistics frozen by one calibration
+ * pass), the crop of every tile and the linear-ramp blend of _tiled_encode / _tiled_decode.  Conventions of the MultiDiffusion calls above:
+ * tables in DEVICE memory, a HOST copy that the call validates (negative code, nothing launched), device rows checked again by the kernels,
+ * no float atomics, bit-equal replays. */
+
+/* mi355x_groupnorm_table -- the statistics passes of mi355x_groupnorm alone (partial sums + finalize, one source, statistics always computed
+ * from x): tab [B][C][2] float32 = (mean of the channel's group, rstd * gamma[c]), the table mi355x_groupnorm's apply pass reads.  raw (may be
+ * NULL): [B][G][2] float32 = (mean, BIASED variance) per group, what FixedGroupNorm keeps as .mean / .var (one more small launch).
+ * ws: mi355x_groupnorm_ws_floats(B, HW, C) floats.  Shape rules of mi355x_groupnorm. */
+typedef struct mi355x_groupnorm_table_args {
+    int32_t dtype;
+    int32_t B, HW, C, G;
+    const void* x;
+    int64_t ldx;
+    const void* gamma;
+    float eps;
+    int32_t reserved;
+    float* ws;
+    float* tab;
+    float* raw;
+} mi355x_groupnorm_table_args;
+int mi355x_groupnorm_table(const mi355x_groupnorm_table_args* a, void* stream);
+
+/* mi355x_groupnorm_fixed -- the apply pass alone, ONE launch: out = (x - tab[c][0]) * tab[c][1] + beta[c] (+ SiLU), with ONE table [C][2] for
+ * every sample of the batch.  With tab = (mean, gamma / sqrt(var + eps)) this is F.batch_norm(training=False) of the grouped tensor followed by
+ * * weight + bias (auto_encoder.py:226-251): the mean is subtracted first, as batch_norm does, so a large mean does not cancel against a folded
+ * shift.  No statistics pass, no workspace.  x, out: [B][HW][C] with pixel strides ldx / ldo; alignment rules of mi355x_groupnorm. */
+typedef struct mi355x_groupnorm_fixed_args {
+    int32_t dtype;
+    int32_t B, HW, C;
+    int32_t silu;
+    int32_t reserved;
+    const void* x;
+    int64_t ldx;
+    const float* tab;
+    const void* beta;
+    void* out;
+    int64_t ldo;
+} mi355x_groupnorm_fixed_args;
+int mi355x_groupnorm_fixed(const mi355x_groupnorm_fixed_args* a, void* stream);
+
+/* mi355x_vae_tile_gather -- T tiles of one size h x w cut out of an NCHW canvas [C][H][W] at pos[t] = (top, left):
+ *   dst[t * s_tile + c * s_c + y * s_y + x * s_x] = c < C ? canvas[c][top + y][left + x] : 0        for c < cpad (cpad >= C)
+ * (s_tile, C h w, w, 1) with cpad == C is the decoder's NCHW latent batch; (h w cpad, 1, w cpad, cpad) is the encoder's token-major first
+ * activation with its channels zero-padded to one K block.  top, left and W are arbitrary (the canvas is read by element); the destination is
+ * written as 16-byte vectors along x (s_x == 1) or along c (s_c == 1) when sizes, strides and the pointer allow, by element otherwise.
+ * dst holds dst_elems elements; a tile outside the canvas or a destination index outside dst: MI355X_ESHAPE; dst overlapping the canvas:
+ * MI355X_EARG. */
+typedef struct mi355x_vae_tile_pos {
+    int32_t top, left;
+} mi355x_vae_tile_pos;
+typedef struct mi355x_vae_gather_args {
+    int32_t dtype;
+    int32_t T, C, cpad, h, w, H, W;
+    const void* canvas;
+    const mi355x_vae_tile_pos* pos;      /* device, T rows */
+    const mi355x_vae_tile_pos* pos_host; /* host copy, validated */
+    void* dst;
+    int64_t dst_elems;
+    int64_t s_tile, s_c, s_y, s_x;
+} mi355x_vae_gather_args;
+int mi355x_vae_tile_gather(const mi355x_vae_gather_args* a, void* stream);
+
+/* mi355x_vae_tile_blend -- result / weights of _tiled_encode / _tiled_decode (auto_encoder.py:480-526, 543-591) in gather form.  The tiles
+ * are the GRID _generate_latent_tiles builds: axis[0 .. nx) = (start, extent) of the columns, axis[nx .. nx + ny) of the rows, start = index *
+ * stride; tile (ix, iy) is row ix * ny + iy of `tiles` (x outer, y inner: the reference's list order).  For every canvas element (c, y, x)
+ * the covering tiles follow from the strides (at most ceil(tile / stride) per axis) and are walked in list order:
+ *   rv = ramp[ty] on the top `ramp_len` rows unless the tile touches the canvas top, ramp[h - 1 - ty] on the bottom ones unless it touches
+ *        the bottom, else 1;  rh likewise from tx;  wgt = rv * rh                      (_create_blending_mask: vertical, then horizontal)
+ *   num += wgt;  cum += wgt * src[off + c * s_c + ty * s_y + tx * s_x]
+ * canvas = cum / num.  One product and one sum each, rounded once, and a correctly rounded division: in float32 the reference's bits; bf16
+ * accumulates in float32 and rounds at the store.  ramp = torch.linspace(0, 1, steps = ramp_len) at ramps[ramp_off], filled by the host;
+ * 2 ramp_len <= min(h, w).  Source strides are explicit: NCHW tiles and token-major rows are both read in place.  An element no tile covers
+ * keeps its value.  One thread owns one element, or four of a row when W % 4 == 0. */
+typedef struct mi355x_vae_axis {
+    int32_t start, extent;
+} mi355x_vae_axis;
+typedef struct mi355x_vae_blend_tile {
+    int64_t off, s_c, s_y, s_x;
+    int32_t ramp_off, ramp_len;
+} mi355x_vae_blend_tile;
+#define MI355X_VAE_MAX_AXIS 1024 /* nx + ny */
+typedef struct mi355x_vae_blend_args {
+    int32_t dtype;
+    int32_t C, H, W;
+    int32_t nx, ny, stride_x, stride_y, tile_w, tile_h;
+    void* canvas;
+    const void* src;
+    int64_t src_elems;
+    const float* ramps;
+    int64_t ramp_elems;
+    const mi355x_vae_axis* axis;            /* device, nx + ny rows */
+    const mi355x_vae_axis* axis_host;       /* host copy, validated */
+    const mi355x_vae_blend_tile* tiles;      /* device, nx * ny rows */
+    const mi355x_vae_blend_tile* tiles_host; /* host copy, validated */
+} mi355x_vae_blend_args;
+int mi355x_vae_tile_blend(const mi355x_vae_blend_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

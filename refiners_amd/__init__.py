@@ -16,3 +16,12 @@ def namespace():
                            ControlLoraAdapter=ControlLoraAdapter, ConditionEncoder=ConditionEncoder, ZeroConvolution=ZeroConvolution, StyleAlignedAdapter=StyleAlignedAdapter,
                            Tile=Tile, Size=Size, DiffusionTarget=DiffusionTarget, MultiDiffusion=MultiDiffusion, SDXLTarget=SDXLTarget,
                            SDXLMultiDiffusion=SDXLMultiDiffusion, SD1DiffusionTarget=SD1DiffusionTarget, SD1MultiDiffusion=SD1MultiDiffusion)
+
+
+def __getattr__(name: str):
+    """`from refiners_amd import CompiledTiledVAE`, resolved on first use (the engine pulls in torch and the native bindings)."""
+    if name == "CompiledTiledVAE":
+        from .engine.tiled_vae import CompiledTiledVAE
+
+        return CompiledTiledVAE
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

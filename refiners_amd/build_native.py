@@ -24,6 +24,8 @@ DEPS = {
     "attention.hip": ["common.cuh"], "attention_general.hip": ["common.cuh"], "norm.hip": ["common.cuh"], "elementwise.hip": ["common.cuh"],
     "sam_decoder.hip": ["common.cuh"], "style_aligned.hip": ["common.cuh"], "multi_diffusion.hip": ["common.cuh"],
 }
+SOURCES += ["tiled_vae.hip"]
+DEPS["tiled_vae.hip"] = ["common.cuh"]
 
 
 def hipcc_path() -> str:

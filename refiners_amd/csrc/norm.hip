@@ -466,3 +466,147 @@ extern "C" int mi355x_groupnorm(const mi355x_groupnorm_args* a, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     return a->dtype == MI355X_F32 ? run_groupnorm<float>(a, st) : run_groupnorm<bf16_t>(a, st);
 }
+
+// ------------------------------------------------------------------------------------------------ GroupNorm with frozen statistics (tiled VAE)
+// FixedGroupNorm (auto_encoder.py:209-251): the statistics of one calibration pass serve every tile.  mi355x_groupnorm_table is the statistics half of
+// mi355x_groupnorm writing to a table the caller keeps, mi355x_groupnorm_fixed the apply half reading ONE table for the whole batch.
+namespace {
+
+// The raw (mean, biased variance) of every group from the pivoted partials of gn_partial_kernel, for comparison with FixedGroupNorm.mean / .var.  One
+// workgroup per (group, sample), thread t sums the chunks of channel t serially in double (calibration only: once per node and image), thread 0 merges
+// the cg channels (Chan).  Fixed order, deterministic.
+template <typename T>
+__global__ __launch_bounds__(256) void gn_raw_stats_kernel(const T* __restrict__ x, int64_t ldx, int HW, int C, int G, int nchunk, const float* __restrict__ part,
+                                                            float* __restrict__ raw) {
+    __shared__ double mean_c[256], m2_c[256];
+    const int g = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+    const int cg = C / G;
+    const double n = (double)HW;
+    if (t < cg) {
+        const int c = g * cg + t;
+        const f32x2* pp = reinterpret_cast<const f32x2*>(part) + ((int64_t)b * nchunk * C + c);
+        double a1 = 0.0, a2 = 0.0;
+        for (int k = 0; k < nchunk; ++k) {
+            const f32x2 v = pp[(int64_t)k * C];
+            a1 += v[0];
+            a2 += v[1];
+        }
+        const double m2 = a2 - a1 * a1 / n;
+        mean_c[t] = (double)to_f32(x[(int64_t)b * HW * ldx + c]) + a1 / n;
+        m2_c[t] = m2 > 0.0 ? m2 : 0.0;
+    }
+    __syncthreads();
+    if (t == 0) {
+        double mg = 0.0, m2 = 0.0;
+        for (int q = 0; q < cg; ++q) mg += mean_c[q];
+        mg /= (double)cg;
+        for (int q = 0; q < cg; ++q) {
+            const double d = mean_c[q] - mg;
+            m2 += m2_c[q] + n * d * d;
+        }
+        raw[((int64_t)b * G + g) * 2 + 0] = (float)mg;
+        raw[((int64_t)b * G + g) * 2 + 1] = (float)(m2 / (n * (double)cg));
+    }
+}
+
+// gn_apply_kernel with one source, ONE table for every sample, and the mean subtracted before the scale: (x - mean) * (rstd gamma) + beta is
+// F.batch_norm(training=False)'s (x - mean) * rstd followed by * weight + bias up to the association of rstd and gamma.
+template <typename T, int U>
+__global__ __launch_bounds__(256) void gn_apply_fixed_kernel(const T* __restrict__ x, int64_t ldx, T* __restrict__ out, int64_t ldo, int HW, int C, int ppc,
+                                                              const float* __restrict__ tab, const T* __restrict__ beta, int silu) {
+    constexpr int EPC = DT<T>::EPC;
+    const int chunk = blockIdx.x, b = blockIdx.y;
+    const int NV = C / EPC;
+    const int tid = threadIdx.x;
+    const int PL = NV >= 256 ? 1 : 256 / NV;
+    const int VPT = NV >= 256 ? (NV + 255) / 256 : 1;
+    const int pl = NV >= 256 ? 0 : tid / NV;
+    const int v0 = NV >= 256 ? tid : tid % NV;
+    if (pl >= PL) return;
+    const int p0 = chunk * ppc;
+    const int p1 = min(p0 + ppc, HW);
+    for (int k = 0; k < VPT; ++k) {
+        const int v = v0 + 256 * k;
+        if (v >= NV) break;
+        float mu[EPC], sc[EPC], bt[EPC];
+        {
+            const f32x2* tb = reinterpret_cast<const f32x2*>(tab) + v * EPC;
+            Vec16<T> bv = load16<T>(beta + v * EPC);
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) {
+                const f32x2 ma = tb[e];
+                mu[e] = ma[0];
+                sc[e] = ma[1];
+                bt[e] = bv.get(e);
+            }
+        }
+        const T* xv = x + (int64_t)b * HW * ldx + v * EPC;
+        T* ov = out + (int64_t)b * HW * ldo + v * EPC;
+        auto emit = [&](const Vec16<T>& t, int px) {
+            Vec16<T> o;
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) {
+                float y = (t.get(e) - mu[e]) * sc[e] + bt[e];
+                if (silu) y = silu_f(y);
+                o.set(e, y);
+            }
+            store16<T>(ov + (int64_t)px * ldo, o);
+        };
+        int px = p0 + pl;
+        for (; px + (U - 1) * PL < p1; px += U * PL) {
+            Vec16<T> t[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) t[u] = load16<T>(xv + (int64_t)(px + u * PL) * ldx);
+#pragma unroll
+            for (int u = 0; u < U; ++u) emit(t[u], px + u * PL);
+        }
+        for (; px < p1; px += PL) emit(load16<T>(xv + (int64_t)px * ldx), px);
+    }
+}
+
+template <typename T>
+int run_groupnorm_table(const mi355x_groupnorm_table_args* a, hipStream_t st) {
+    const int ppc = gn_ppc(a->B, a->HW, a->C, sizeof(T));
+    const int nchunk = (a->HW + ppc - 1) / ppc;
+    const T* x = static_cast<const T*>(a->x);
+    hipLaunchKernelGGL((gn_partial_kernel<T>), dim3(nchunk, a->B), dim3(256), 0, st, x, a->ldx, static_cast<const T*>(nullptr), (int64_t)0, a->C, a->HW, a->C, ppc, nchunk, a->ws);
+    hipLaunchKernelGGL((gn_finalize_kernel<T>), dim3(a->G, a->B), dim3(256), 0, st, x, a->ldx, static_cast<const T*>(nullptr), (int64_t)0, a->C, a->HW, a->C, a->G, nchunk,
+                       a->ws, static_cast<const T*>(a->gamma), a->eps, a->tab);
+    if (a->raw) hipLaunchKernelGGL((gn_raw_stats_kernel<T>), dim3(a->G, a->B), dim3(256), 0, st, x, a->ldx, a->HW, a->C, a->G, nchunk, a->ws, a->raw);
+    return hipGetLastError() == hipSuccess ? MI355X_OK : MI355X_ELAUNCH;
+}
+
+template <typename T>
+int run_groupnorm_fixed(const mi355x_groupnorm_fixed_args* a, hipStream_t st) {
+    const int ppc = gn_ppc(a->B, a->HW, a->C, sizeof(T));
+    const int nchunk = (a->HW + ppc - 1) / ppc;
+    hipLaunchKernelGGL((gn_apply_fixed_kernel<T, 4>), dim3(nchunk, a->B), dim3(256), 0, st, static_cast<const T*>(a->x), a->ldx, static_cast<T*>(a->out), a->ldo, a->HW, a->C, ppc,
+                       a->tab, static_cast<const T*>(a->beta), a->silu);
+    return hipGetLastError() == hipSuccess ? MI355X_OK : MI355X_ELAUNCH;
+}
+
+}  // namespace
+
+extern "C" int mi355x_groupnorm_table(const mi355x_groupnorm_table_args* a, void* stream) {
+    if (!a || !a->x || !a->gamma || !a->ws || !a->tab) return MI355X_EARG;
+    if (a->dtype != MI355X_F32 && a->dtype != MI355X_BF16) return MI355X_EDTYPE;
+    const int es = a->dtype == MI355X_F32 ? 4 : 2;
+    if (a->B <= 0 || a->HW <= 0 || a->C <= 0 || a->G <= 0 || a->C % a->G) return MI355X_ESHAPE;
+    if ((a->C * es) % 16 || (a->ldx * es) % 16 || a->ldx < a->C) return MI355X_ESHAPE;
+    if ((a->C * es) / 16 > 256 * GN_MAXVPT || a->C / a->G > 256) return MI355X_ESHAPE;
+    if (!al16(a->x) || (reinterpret_cast<uintptr_t>(a->tab) & 7) || (reinterpret_cast<uintptr_t>(a->ws) & 7)) return MI355X_ESHAPE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return a->dtype == MI355X_F32 ? run_groupnorm_table<float>(a, st) : run_groupnorm_table<bf16_t>(a, st);
+}
+
+extern "C" int mi355x_groupnorm_fixed(const mi355x_groupnorm_fixed_args* a, void* stream) {
+    if (!a || !a->x || !a->out || !a->tab || !a->beta) return MI355X_EARG;
+    if (a->dtype != MI355X_F32 && a->dtype != MI355X_BF16) return MI355X_EDTYPE;
+    const int es = a->dtype == MI355X_F32 ? 4 : 2;
+    if (a->B <= 0 || a->HW <= 0 || a->C <= 0) return MI355X_ESHAPE;
+    if ((a->C * es) % 16 || (a->ldx * es) % 16 || (a->ldo * es) % 16 || a->ldx < a->C || a->ldo < a->C) return MI355X_ESHAPE;
+    if ((a->C * es) / 16 > 256 * GN_MAXVPT) return MI355X_ESHAPE;
+    if (!al16(a->x) || !al16(a->out) || !al16(a->beta) || (reinterpret_cast<uintptr_t>(a->tab) & 7)) return MI355X_ESHAPE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return a->dtype == MI355X_F32 ? run_groupnorm_fixed<float>(a, st) : run_groupnorm_fixed<bf16_t>(a, st);
+}

@@ -338,6 +338,50 @@ class MdBlendArgs(C.Structure):
     ]
 
 
+class GroupNormTableArgs(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int32), ("B", C.c_int32), ("HW", C.c_int32), ("C", C.c_int32), ("G", C.c_int32),
+        ("x", C.c_void_p), ("ldx", C.c_int64), ("gamma", C.c_void_p), ("eps", C.c_float), ("reserved", C.c_int32),
+        ("ws", C.c_void_p), ("tab", C.c_void_p), ("raw", C.c_void_p),
+    ]
+
+
+class GroupNormFixedArgs(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int32), ("B", C.c_int32), ("HW", C.c_int32), ("C", C.c_int32), ("silu", C.c_int32), ("reserved", C.c_int32),
+        ("x", C.c_void_p), ("ldx", C.c_int64), ("tab", C.c_void_p), ("beta", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_int64),
+    ]
+
+
+class VaeTilePos(C.Structure):
+    _fields_ = [("top", C.c_int32), ("left", C.c_int32)]
+
+
+class VaeGatherArgs(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int32), ("T", C.c_int32), ("C", C.c_int32), ("cpad", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("canvas", C.c_void_p), ("pos", C.c_void_p), ("pos_host", C.c_void_p), ("dst", C.c_void_p), ("dst_elems", C.c_int64),
+        ("s_tile", C.c_int64), ("s_c", C.c_int64), ("s_y", C.c_int64), ("s_x", C.c_int64),
+    ]
+
+
+class VaeAxis(C.Structure):
+    _fields_ = [("start", C.c_int32), ("extent", C.c_int32)]
+
+
+class VaeBlendTile(C.Structure):
+    _fields_ = [("off", C.c_int64), ("s_c", C.c_int64), ("s_y", C.c_int64), ("s_x", C.c_int64), ("ramp_off", C.c_int32), ("ramp_len", C.c_int32)]
+
+
+class VaeBlendArgs(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("nx", C.c_int32), ("ny", C.c_int32), ("stride_x", C.c_int32), ("stride_y", C.c_int32), ("tile_w", C.c_int32), ("tile_h", C.c_int32),
+        ("canvas", C.c_void_p), ("src", C.c_void_p), ("src_elems", C.c_int64), ("ramps", C.c_void_p), ("ramp_elems", C.c_int64),
+        ("axis", C.c_void_p), ("axis_host", C.c_void_p), ("tiles", C.c_void_p), ("tiles_host", C.c_void_p),
+    ]
+
+
 #: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "mi355x_abi_version",
@@ -375,6 +419,10 @@ EXPORTS = [
     "mi355x_md_gather",
     "mi355x_md_target_step",
     "mi355x_md_blend",
+    "mi355x_groupnorm_table",
+    "mi355x_groupnorm_fixed",
+    "mi355x_vae_tile_gather",
+    "mi355x_vae_tile_blend",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -437,6 +485,10 @@ def load(path: Optional[Path] = None) -> C.CDLL:
     lib.mi355x_md_gather.argtypes = [C.POINTER(MdGatherArgs), C.c_void_p]
     lib.mi355x_md_target_step.argtypes = [C.POINTER(MdStepArgs), C.c_void_p]
     lib.mi355x_md_blend.argtypes = [C.POINTER(MdBlendArgs), C.c_void_p]
+    lib.mi355x_groupnorm_table.argtypes = [C.POINTER(GroupNormTableArgs), C.c_void_p]
+    lib.mi355x_groupnorm_fixed.argtypes = [C.POINTER(GroupNormFixedArgs), C.c_void_p]
+    lib.mi355x_vae_tile_gather.argtypes = [C.POINTER(VaeGatherArgs), C.c_void_p]
+    lib.mi355x_vae_tile_blend.argtypes = [C.POINTER(VaeBlendArgs), C.c_void_p]
     lib.mi355x_set_option.argtypes = [C.c_char_p, C.c_int]
     lib.mi355x_attention_set_glds.argtypes = [C.c_int]
     lib.mi355x_attention_general_set_fast.argtypes = [C.c_int]
@@ -1511,6 +1563,101 @@ def md_blend(canvas: Tensor, stepped: Tensor, desc: Tensor, desc_host: Tensor, n
     a.dtype, a.n_targets, (a.C, a.H, a.W) = dtype_code(canvas.dtype), n_targets, canvas.shape[1:]
     a.canvas, a.stepped, a.stepped_elems, a.desc, a.desc_host = canvas.data_ptr(), stepped.data_ptr(), stepped.numel(), desc.data_ptr(), desc_host.data_ptr()
     _launch("mi355x_md_blend", (C.byref(a),), "mi355x_md_blend", keep=(a, canvas, stepped, desc, desc_host))
+    return canvas
+
+
+# ------------------------------------------------------------------------------------------------ tiled VAE (csrc/norm.hip, csrc/tiled_vae.hip)
+VAE_POS_BYTES, VAE_AXIS_BYTES, VAE_BLEND_TILE_BYTES = C.sizeof(VaeTilePos), C.sizeof(VaeAxis), C.sizeof(VaeBlendTile)
+VAE_MAX_AXIS = 1024
+
+
+def groupnorm_table(x: Tensor, gamma: Tensor, groups: int, eps: float, tab: Tensor, raw: Optional[Tensor] = None, ws: Optional[Tensor] = None) -> Tensor:
+    """x [B, HW, C] (contiguous channels) -> tab float32 [B, C, 2] = (group mean, rstd * gamma), the table GroupNorm's apply pass reads; raw float32
+    [B, G, 2] = (mean, biased variance) per group when given.  See mi355x_groupnorm_table."""
+    B, HW, Cc = x.shape
+    assert x.stride(2) == 1 and x.stride(0) == HW * x.stride(1) and gamma.dtype == x.dtype and gamma.numel() == Cc
+    assert tab.dtype == torch.float32 and tab.is_contiguous() and tab.numel() == B * Cc * 2
+    assert raw is None or (raw.dtype == torch.float32 and raw.is_contiguous() and raw.numel() == B * groups * 2)
+    need = load().mi355x_groupnorm_ws_floats(B, HW, Cc)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.float32, device=x.device)
+    assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= need
+    a = GroupNormTableArgs()
+    a.dtype, a.B, a.HW, a.C, a.G = dtype_code(x.dtype), B, HW, Cc, groups
+    a.x, a.ldx, a.gamma, a.eps, a.ws, a.tab, a.raw = x.data_ptr(), x.stride(1), gamma.data_ptr(), eps, ws.data_ptr(), tab.data_ptr(), None if raw is None else raw.data_ptr()
+    _launch("mi355x_groupnorm_table", (C.byref(a),), "mi355x_groupnorm_table", keep=(a, x, gamma, ws, tab, raw))
+    return tab
+
+
+def groupnorm_fixed(x: Tensor, tab: Tensor, beta: Tensor, silu: bool, out: Tensor) -> Tensor:
+    """out = (x - tab[c, 0]) * tab[c, 1] + beta[c] (+ SiLU) with ONE float32 table [C, 2] for every sample of x [B, HW, C].  See mi355x_groupnorm_fixed."""
+    B, HW, Cc = x.shape
+    assert x.stride(2) == 1 and out.stride(2) == 1 and x.stride(0) == HW * x.stride(1) and out.stride(0) == HW * out.stride(1) and out.shape == x.shape and out.dtype == x.dtype
+    assert tab.dtype == torch.float32 and tab.is_contiguous() and tab.numel() == Cc * 2 and beta.dtype == x.dtype and beta.numel() == Cc
+    a = GroupNormFixedArgs()
+    a.dtype, a.B, a.HW, a.C, a.silu = dtype_code(x.dtype), B, HW, Cc, int(silu)
+    a.x, a.ldx, a.tab, a.beta, a.out, a.ldo = x.data_ptr(), x.stride(1), tab.data_ptr(), beta.data_ptr(), out.data_ptr(), out.stride(1)
+    _launch("mi355x_groupnorm_fixed", (C.byref(a),), "mi355x_groupnorm_fixed", keep=(a, x, tab, beta, out))
+    return out
+
+
+def vae_pos_rows(rows: list) -> Tensor:
+    """[(top, left)] -> the position rows of mi355x_vae_tile_gather as a uint8 CPU tensor [T, 8]."""
+    arr = (VaeTilePos * len(rows))()
+    for d, (top, left) in zip(arr, rows):
+        d.top, d.left = int(top), int(left)
+    return _md_rows(arr, len(rows), VAE_POS_BYTES)
+
+
+def vae_axis_rows(xs: list, ys: list) -> Tensor:
+    """[(start, extent)] of the columns, then of the rows -> the axis table of mi355x_vae_tile_blend as a uint8 CPU tensor [nx + ny, 8]."""
+    arr = (VaeAxis * (len(xs) + len(ys)))()
+    for d, (start, extent) in zip(arr, list(xs) + list(ys)):
+        d.start, d.extent = int(start), int(extent)
+    return _md_rows(arr, len(xs) + len(ys), VAE_AXIS_BYTES)
+
+
+def vae_blend_rows(rows: list) -> Tensor:
+    """[(off, s_c, s_y, s_x, ramp_off, ramp_len)] in list order (ix * ny + iy) -> the tile rows of mi355x_vae_tile_blend as a uint8 CPU tensor [T, 40]."""
+    arr = (VaeBlendTile * len(rows))()
+    for d, (off, s_c, s_y, s_x, ramp_off, ramp_len) in zip(arr, rows):
+        d.off, d.s_c, d.s_y, d.s_x, d.ramp_off, d.ramp_len = int(off), int(s_c), int(s_y), int(s_x), int(ramp_off), int(ramp_len)
+    return _md_rows(arr, len(rows), VAE_BLEND_TILE_BYTES)
+
+
+def _table_pair(dev: Tensor, host: Tensor, nbytes: int, like: Tensor) -> None:
+    assert dev.dtype == torch.uint8 and dev.is_contiguous() and dev.numel() >= nbytes and dev.device == like.device
+    assert host.dtype == torch.uint8 and host.is_contiguous() and host.numel() >= nbytes and host.device.type == "cpu"
+
+
+def vae_tile_gather(canvas: Tensor, pos: Tensor, pos_host: Tensor, dst: Tensor, T: int, hw: tuple[int, int], strides: tuple[int, int, int, int], cpad: Optional[int] = None) -> None:
+    """canvas [1, C, H, W] (contiguous); T tiles of hw = (h, w) at the (top, left) rows of pos / pos_host (device / host, vae_pos_rows) -> dst, any contiguous
+    tensor of the canvas dtype, written at t * s_tile + c * s_c + y * s_y + x * s_x for strides = (s_tile, s_c, s_y, s_x); channels [C, cpad) are zeros.
+    See mi355x_vae_tile_gather."""
+    assert canvas.dim() == 4 and canvas.shape[0] == 1 and canvas.is_contiguous() and dst.is_contiguous() and dst.dtype == canvas.dtype
+    _table_pair(pos, pos_host, T * VAE_POS_BYTES, canvas)
+    a = VaeGatherArgs()
+    a.dtype, a.T, a.C, a.cpad, (a.h, a.w), (a.H, a.W) = dtype_code(canvas.dtype), T, canvas.shape[1], canvas.shape[1] if cpad is None else cpad, hw, canvas.shape[2:]
+    a.canvas, a.pos, a.pos_host, a.dst, a.dst_elems = canvas.data_ptr(), pos.data_ptr(), pos_host.data_ptr(), dst.data_ptr(), dst.numel()
+    a.s_tile, a.s_c, a.s_y, a.s_x = strides
+    _launch("mi355x_vae_tile_gather", (C.byref(a),), "mi355x_vae_tile_gather", keep=(a, canvas, pos, pos_host, dst))
+
+
+def vae_tile_blend(canvas: Tensor, src: Tensor, ramps: Tensor, axis: Tensor, axis_host: Tensor, tiles: Tensor, tiles_host: Tensor, nxy: tuple[int, int],
+                   stride_xy: tuple[int, int], tile_wh: tuple[int, int]) -> Tensor:
+    """canvas [1, C, H, W] <- the ramp-weighted mean of the grid's tiles, read from src (any contiguous tensor of the canvas dtype) at each tile row's offset
+    and strides.  ramps: float32 device tensor of the linspace tables; axis / tiles: device uint8 tables of vae_axis_rows / vae_blend_rows with their host
+    copies.  See mi355x_vae_tile_blend."""
+    assert canvas.dim() == 4 and canvas.shape[0] == 1 and canvas.is_contiguous() and src.is_contiguous() and src.dtype == canvas.dtype
+    assert ramps.dtype == torch.float32 and ramps.is_contiguous() and ramps.device == canvas.device
+    nx, ny = nxy
+    _table_pair(axis, axis_host, (nx + ny) * VAE_AXIS_BYTES, canvas)
+    _table_pair(tiles, tiles_host, nx * ny * VAE_BLEND_TILE_BYTES, canvas)
+    a = VaeBlendArgs()
+    a.dtype, (a.C, a.H, a.W), (a.nx, a.ny), (a.stride_x, a.stride_y), (a.tile_w, a.tile_h) = dtype_code(canvas.dtype), canvas.shape[1:], nxy, stride_xy, tile_wh
+    a.canvas, a.src, a.src_elems, a.ramps, a.ramp_elems = canvas.data_ptr(), src.data_ptr(), src.numel(), ramps.data_ptr() if ramps.numel() else None, ramps.numel()
+    a.axis, a.axis_host, a.tiles, a.tiles_host = axis.data_ptr(), axis_host.data_ptr(), tiles.data_ptr(), tiles_host.data_ptr()
+    _launch("mi355x_vae_tile_blend", (C.byref(a),), "mi355x_vae_tile_blend", keep=(a, canvas, src, ramps, axis, axis_host, tiles, tiles_host))
     return canvas
 
 
