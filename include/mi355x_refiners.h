@@ -112,7 +112,8 @@ typedef struct {
     const void* res;        /* [M][ldres] or NULL */
     int64_t ldres;
     const void* zeros;      /* >= 256 zero bytes in device memory; required when conv == 1 */
-    int32_t tile;           /* 0 = let the library choose; 1: 128x128  2: 128x64  3: 64x128  4: 64x64 (M x N);
+    int32_t tile;           /* (the rules below live in ONE table: refiners_amd/csrc/gemm_tiles.cuh, mirrored for Python by refiners_amd/engine/tiles.py)
+                               0 = let the library choose; 1: 128x128  2: 128x64  3: 64x128  4: 64x64 (M x N);
                                6: 128x128 computed by 8 waves in two K groups (even / odd K blocks, summed through LDS in a fixed order):
                                for launches with fewer output tiles than CUs;
                                7: 256x256 on the 8-wave / eight-phase main loop (one workgroup per CU, counted LDS-DMA waits, the two halves of the

@@ -1,6 +1,7 @@
 // mi355x_gemm: C entry point, argument validation and the plain-GEMM instantiations of gemm_kernel.cuh.
 // (The implicit-GEMM convolution instantiations live in gemm_conv.hip so that the two halves compile in parallel.)
 #include <climits>
+#include <cstring>
 
 #include "gemm8_kernel.cuh"
 #include "gemm_kernel.cuh"
@@ -17,6 +18,15 @@ int g_g8_persist = 1;
 
 namespace {
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+int cu_count() {  // of the current device
+    static int n_cu[64] = {};
+    int dev = 0, n = 0;
+    (void)hipGetDevice(&dev);
+    if (dev >= 0 && dev < 64 && n_cu[dev]) return n_cu[dev];
+    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    if (dev >= 0 && dev < 64) n_cu[dev] = n;
+    return n;
+}
 }  // namespace
 
 }  // namespace mi355x
@@ -27,51 +37,37 @@ extern "C" int mi355x_set_option(const char* name, int value);
 extern "C" int mi355x_set_option(const char* name, int value) {
     // debugging / A-B switches; not part of the stable contract
     if (!name) return MI355X_EARG;
-    if (name[0] == 'g' && name[1] == 'n') {  // "gnwgs" / "gnunroll" (norm.hip)
-        extern int g_gn_wgs, g_gn_unroll;
-        if (name[2] == 'w') g_gn_wgs = value;
-        else g_gn_unroll = value;
+    extern int g_gn_wgs, g_gn_unroll;  // (norm.hip)
+    const struct { const char* name; int* var; } opts[] = {{"gnwgs", &g_gn_wgs}, {"gnunroll", &g_gn_unroll}, {"g8persist", &g_g8_persist}, {"skg", &g_sk_g},  // "skg": number of stream-K workgroups (0 = one per CU)
+                                                          {"stages", &g_stages}, {"pfmode", &g_pf_mode}, {"lora_dbg", &g_lora_dbg}, {"tile", &g_tile}};
+    if (!strcmp(name, "pfblocks")) {
+        g_pf_blocks = value < 0 ? 0 : (value + 7) / 8 * 8;
         return MI355X_OK;
     }
-    if (name[0] == 'g' && name[1] == '8') {  // "g8persist"
-        g_g8_persist = value;
-        return MI355X_OK;
-    }
-    if (name[0] == 's' && name[1] == 'k') {  // "skg": number of stream-K workgroups (0 = one per CU)
-        g_sk_g = value;
-        return MI355X_OK;
-    }
-    if (name[0] == 's') {  // "stages"
-        g_stages = value;
-        return MI355X_OK;
-    }
-    if (name[0] == 'p') {  // "pfblocks" / "pfmode"
-        if (name[2] == 'b') g_pf_blocks = value < 0 ? 0 : (value + 7) / 8 * 8;
-        else g_pf_mode = value;
-        return MI355X_OK;
-    }
-    if (name[0] == 'l') {  // "lora_dbg"
-        g_lora_dbg = value;
-        return MI355X_OK;
-    }
-    if (name[0] == 't') {  // "tile"
-        g_tile = value;
-        return MI355X_OK;
-    }
+    for (const auto& o : opts)
+        if (!strcmp(name, o.name)) {
+            *o.var = value;
+            return MI355X_OK;
+        }
     return MI355X_EARG;
 }
 
-static int g_stat_g8 = 0, g_stat_g8_lora = 0, g_stat_g9 = 0, g_stat_g11 = 0, g_stat_g12 = 0;
+static int g_stat_tile[32] = {}, g_stat_g8_lora = 0;  // launches per tile id of the 8-wave loop (gemm_tiles.cuh), and those of them with the in-launch LoRA
 extern "C" int mi355x_get_stat(const char* name);
 extern "C" int mi355x_get_stat(const char* name) {
     // launches since the library was loaded (tests: did the configuration asked for really run?); like mi355x_set_option not part of the stable contract
-    //   "g8" = launches on the 8-wave loop (tile configurations 7 / 8 / 9), "g8lora" = those of them with the in-launch LoRA, "g9" = those on 192-row tiles,
+    //   "g8" = launches on the 8-wave loop (every tile configuration of it), "g8lora" = those of them with the in-launch LoRA, "g9" = those on 192-row tiles,
     //   "g11" / "g12" = those on tile configuration 11 / 12
     if (!name) return MI355X_EARG;
-    if (name[0] == 'g' && name[1] == '8') return name[2] == 'l' ? g_stat_g8_lora : g_stat_g8;
-    if (name[0] == 'g' && name[1] == '9') return g_stat_g9;
-    if (name[0] == 'g' && name[1] == '1' && name[2] == '1') return g_stat_g11;
-    if (name[0] == 'g' && name[1] == '1' && name[2] == '2') return g_stat_g12;
+    if (!strcmp(name, "g8lora")) return g_stat_g8_lora;
+    if (!strcmp(name, "g8")) {
+        int n = 0;
+        for (const Tile& t : TILES) n += t.loop == 8 ? g_stat_tile[t.id] : 0;
+        return n;
+    }
+    if (!strcmp(name, "g9")) return g_stat_tile[9];
+    if (!strcmp(name, "g11")) return g_stat_tile[11];
+    if (!strcmp(name, "g12")) return g_stat_tile[12];
     return MI355X_EARG;
 }
 
@@ -242,48 +238,16 @@ extern "C" int mi355x_gemm(const mi355x_gemm_args* a, void* stream) {
         }
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int tile_req = g_tile ? g_tile : a->tile;
-    if (tile_req == 0 && a->dtype == MI355X_BF16 && p.ksplit == 1 && p.N % 320 == 0 && p.N % 256 != 0) {
-        // nobody chose: where 256-column tiles waste MFMA work (N = 320 / 640 / 960 / 1920) and 128 x 320 tiles of the 8-wave loop fill the CUs in whole rounds
-        // (the level-1 convolutions of a CFG pair: 256 tiles), those -- hot 1.1-1.4x, in place -0.3 ms per step over the six classes
-        int dev = 0, ncu = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        const int64_t t12 = (int64_t)((p.M + 127) / 128) * (p.N / 320);
-        if (ncu > 0 && t12 % ncu == 0 && gemm8_ok(p, a->conv != 0, 12)) tile_req = 12;
-    }
-    int g8_mt = tile_req == 9 ? 6 : tile_req == 10 ? 4 : tile_req == 12 ? 12 : 8;  // tile 9: the same loop on 192 x 256 tiles (whole tiles only); 10: on 128 x 256 tiles (bf16 GEMMs);
-                                                                                  // 12: on 128 x 320 tiles (bf16 GEMMs and convolutions)
-    bool want_g8 = tile_req == 7 || tile_req == 8 || tile_req == 9 || (tile_req == 10 && a->dtype == MI355X_BF16 && !a->conv) || (tile_req == 12 && a->dtype == MI355X_BF16);
-    if (tile_req == 11) {  // 192-row tiles for a whole number of rounds + 128-row tiles for a whole number of rounds (bf16 GEMMs whose shape admits it: plan_mix); else tile 9
-        int rb, cb, nb, ns, dev = 0, ncu = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        want_g8 = true;
-        g8_mt = a->dtype == MI355X_BF16 && !a->conv && g_sk_g == 0 && plan_mix(p.M, p.N, ncu, rb, cb, nb, ns) ? 11 : 6;
-    }
-    if (want_g8 && p.ksplit > 1) {
-        // a caller that split K for want of tiles AND asks for the 8-wave loop (native._fill_split: the measured table replaced a heuristic split): the loop needs
-        // no split (whole tiles or stream-K) -- take it unsplit where it can run, otherwise keep the split on the 128 x 128 tile of the 4-wave kernel
-        GemmP q = p;
-        q.ksplit = 1;
-        q.kb_per_split = 0;
-        q.partial = nullptr;
-        if (gemm8_ok(q, a->conv != 0, g8_mt)) p = q;
-        else p.tile_hint = 1;
-    }
-    if (want_g8 && gemm8_ok(p, a->conv != 0, g8_mt)) {  // the 8-wave / eight-phase loop (gemm8_kernel.cuh); otherwise the heuristic decides
-        ++g_stat_g8;
+    const int ncu = cu_count();
+    const bool sk_scratch = a->sk_ws && a->sk_flags && a->sk_slots > 0 && (reinterpret_cast<uintptr_t>(a->sk_ws) & 15) == 0;
+    if (const Tile* t = resolve_tile(g_tile ? g_tile : a->tile, p, a->conv != 0, a->dtype == MI355X_F32, ncu, sk_scratch)) {  // the 8-wave / eight-phase loop (gemm8_kernel.cuh); otherwise the heuristic decides
+        ++g_stat_tile[t->id];
         if (p.lora_b) ++g_stat_g8_lora;
-        if (g8_mt == 6) ++g_stat_g9;
-        if (g8_mt == 11) ++g_stat_g11;
-        if (g8_mt == 12) ++g_stat_g12;
-        const bool sk = tile_req == 8 && a->sk_ws && a->sk_flags && a->sk_slots > 0 && (reinterpret_cast<uintptr_t>(a->sk_ws) & 15) == 0;
         p.sk_ws = static_cast<float*>(a->sk_ws);
         p.sk_flags = a->sk_flags;
         p.sk_cap = a->sk_slots;
-        if (a->conv) return a->dtype == MI355X_F32 ? launch_conv8_f32(p, st, sk, g8_mt) : launch_conv8_bf16(p, st, sk, g8_mt);
-        return a->dtype == MI355X_F32 ? launch_gemm8_f32(p, st, sk, g8_mt) : launch_gemm8_bf16(p, st, sk, g8_mt);
+        if (a->conv) return a->dtype == MI355X_F32 ? launch_conv8_f32(p, st, *t) : launch_conv8_bf16(p, st, *t);
+        return a->dtype == MI355X_F32 ? launch_gemm8_f32(p, st, *t) : launch_gemm8_bf16(p, st, *t);
     }
     if (a->conv) return a->dtype == MI355X_F32 ? launch_conv_f32(p, st) : launch_conv_bf16(p, st);
     if (a->dtype == MI355X_F32) return launch_tile<float, false>(p, st);

@@ -43,6 +43,7 @@
 
 #include "gemm_epilogue.cuh"
 #include "gemm_lora_producer.cuh"
+#include "gemm_tiles.cuh"
 
 namespace mi355x {
 
@@ -748,27 +749,8 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmP p) {
     }
 }
 
-extern int g_sk_g;        // probing: number of stream-K / persistent workgroups (0 = one per CU)
 extern int g_lora_dbg;    // probing bits of the in-launch LoRA (gemm.hip; bit 0 = the hand-over's producers exit at once)
 extern int g_g8_persist;  // 1 = launches with more tiles than CUs run as one persistent workgroup per CU
-
-// Geometry of a two-height launch (tile id 11) for n_cu CUs, or false: rows [0, rb) in 192-row tiles over the first cb column tiles = a whole number of rounds, everything else in
-// 128-row tiles = a whole number of rounds, each XCD with whole column tiles of every region (mix_coords).
-inline bool plan_mix(int M, int N, int n_cu, int& rb, int& cb, int& nbig, int& nsmall) {
-    if (M <= 0 || N <= 0 || M % 128 || N % 256 || n_cu <= 0 || n_cu % 8) return false;
-    const int tn = N / 256;
-    if (tn % 8) return false;
-    for (rb = M / 384 * 384; rb >= 384; rb -= 384) {
-        if ((M - rb) % 128) continue;
-        const int rows_big = rb / 192;
-        for (cb = tn / 8 * 8 - 8; cb >= 8; cb -= 8) {
-            nbig = rows_big * cb;
-            nsmall = (rb / 128) * (tn - cb) + ((M - rb) / 128) * tn;
-            if (nbig % n_cu == 0 && nsmall % n_cu == 0) return true;
-        }
-    }
-    return false;
-}
 
 template <typename T, bool CONV, bool LORA, int MT, int MT2 = 0, int NT = 4>
 int launch_gemm8_impl(const GemmP& p, hipStream_t stream, bool streamk) {
@@ -853,43 +835,34 @@ int launch_gemm8_impl(const GemmP& p, hipStream_t stream, bool streamk) {
     return hipGetLastError() == hipSuccess ? MI355X_OK : MI355X_ELAUNCH;
 }
 
+// The instance a row of the 8-wave loop (gemm_tiles.cuh) runs on.  A row selects among these; a new row needs its instance here.
 template <typename T, bool CONV>
-int launch_gemm8(const GemmP& p, hipStream_t stream, bool streamk, int mt) {  // mt: 8 = 256-row tiles (tile ids 7 / 8), 6 = 192-row tiles (tile id 9), 4 = 128-row tiles (tile id 10: bf16 GEMMs only), 11 = 192- and 128-row tiles in one launch (tile id 11),
-                                                                                //     12 = 128 x 320 tiles (tile id 12: bf16 GEMMs and convolutions, whole tiles)
-    if (mt == 12) {
-        if constexpr (sizeof(T) == 2) return launch_gemm8_impl<T, CONV, false, 4, 0, 5>(p, stream, false);
-        return MI355X_ESHAPE;
+int launch_gemm8(const GemmP& p, hipStream_t stream, const Tile& t) {
+    const bool streamk = t.streamk != 0;
+    switch (t.id) {
+        case 12:  // 128 x 320
+            if constexpr (sizeof(T) == 2) return launch_gemm8_impl<T, CONV, false, 4, 0, 5>(p, stream, false);
+            return MI355X_ESHAPE;
+        case 11:  // 192- and 128-row tiles in one launch
+            if constexpr (!CONV && sizeof(T) == 2) return p.lora_b ? launch_gemm8_impl<T, false, true, 6, 4>(p, stream, false) : launch_gemm8_impl<T, false, false, 6, 4>(p, stream, false);
+            return MI355X_ESHAPE;
+        case 10:  // 128 x 256
+            if constexpr (!CONV && sizeof(T) == 2) return p.lora_b ? launch_gemm8_impl<T, false, true, 4>(p, stream, false) : launch_gemm8_impl<T, false, false, 4>(p, stream, false);
+            return MI355X_ESHAPE;
+        default: break;
     }
-    if constexpr (!CONV && sizeof(T) == 2) {
-        if (mt == 11) return p.lora_b ? launch_gemm8_impl<T, false, true, 6, 4>(p, stream, false) : launch_gemm8_impl<T, false, false, 6, 4>(p, stream, false);
-        if (mt == 4) return p.lora_b ? launch_gemm8_impl<T, false, true, 4>(p, stream, false) : launch_gemm8_impl<T, false, false, 4>(p, stream, false);
-    }
+    // 9: 192 x 256;  7 / 8: 256 x 256, whole tiles / stream-K
     if constexpr (!CONV) {
         if (p.lora_b) {  // (its own instance: the LoRA roles cost the plain one registers it does not have)
-            return mt == 6 ? launch_gemm8_impl<T, false, true, 6>(p, stream, false) : launch_gemm8_impl<T, false, true, 8>(p, stream, streamk);
+            return t.id == 9 ? launch_gemm8_impl<T, false, true, 6>(p, stream, false) : launch_gemm8_impl<T, false, true, 8>(p, stream, streamk);
         }
     }
-    return mt == 6 ? launch_gemm8_impl<T, CONV, false, 6>(p, stream, false) : launch_gemm8_impl<T, CONV, false, 8>(p, stream, streamk);
+    return t.id == 9 ? launch_gemm8_impl<T, CONV, false, 6>(p, stream, false) : launch_gemm8_impl<T, CONV, false, 8>(p, stream, streamk);
 }
 
-// Can this launch run on the 8-phase loop?  (No in-launch LoRA, no split-K workspace protocol, transposed column groups from a multiple of 256; every operand below
-// 2 GB: 32-bit buffer offsets with 0x80000000 as the out-of-range marker.)
-inline bool gemm8_ok(const GemmP& p, bool conv = false, int mt = 8) {
-    if (mt != 8 && p.out_t) return false;  // (the 192- and 128-row tiles have no transposed form)
-    // (the 320-column tiles run the plain, bias, row-bias, activation, residual and column-statistics epilogues, without in-launch LoRA)
-    if (mt == 12 && (p.lora_b || p.ln_stats || p.geglu || p.stats_out || p.out_f32)) return false;
-    if (mt == 4 && conv) return false;  // (tile id 10 is instantiated for bf16 GEMMs: gemm.hip keeps float32 launches off it)
-    if (p.ksplit > 1 || !p.vec_ok || p.N % 16) return false;  // (the epilogue instances of this loop are the vectorised ones)
-    if (p.lora_b && (conv || p.lora_groups != 1 || p.nseg != 1 || p.out_t || (p.lora_r != 32 && p.lora_r != 64 && p.lora_r != 128) || !p.lora_t || !p.lora_flags || !p.lora_epoch)) return false;  // in-launch LoRA here: one column group of a plain GEMM
-    if (p.out_t && p.nt_begin % 256) return false;  // a tile is either stored row-major or transposed
-    for (int s = 0; s < p.nseg; ++s)
-        if (p.seg[s].xbytes <= 0 || p.seg[s].wbytes <= 0 || p.seg[s].xbytes >= (1ll << 31) || p.seg[s].wbytes >= (1ll << 31)) return false;
-    return true;
-}
-
-int launch_gemm8_f32(const GemmP& p, hipStream_t stream, bool streamk, int mt);
-int launch_gemm8_bf16(const GemmP& p, hipStream_t stream, bool streamk, int mt);
-int launch_conv8_f32(const GemmP& p, hipStream_t stream, bool streamk, int mt);
-int launch_conv8_bf16(const GemmP& p, hipStream_t stream, bool streamk, int mt);
+int launch_gemm8_f32(const GemmP& p, hipStream_t stream, const Tile& t);
+int launch_gemm8_bf16(const GemmP& p, hipStream_t stream, const Tile& t);
+int launch_conv8_f32(const GemmP& p, hipStream_t stream, const Tile& t);
+int launch_conv8_bf16(const GemmP& p, hipStream_t stream, const Tile& t);
 
 }  // namespace mi355x

@@ -44,6 +44,7 @@
 #pragma once
 #include "gemm_epilogue.cuh"
 #include "gemm_lora_producer.cuh"
+#include "gemm_tiles.cuh"
 
 namespace mi355x {
 
@@ -715,8 +716,10 @@ int launch_cfg(const GemmP& p, hipStream_t stream) {
 // how many workgroups a configuration yields: big tiles reuse operands better, small tiles fill the machine.  The engine
 // passes measured choices per shape (refiners_amd/engine/tuning.py); this heuristic is the fallback.
 inline int pick_tile(const GemmP& p, bool conv) {
-    if ((g_tile >= 1 && g_tile <= 4) || g_tile == 6) return g_tile;
-    if ((p.tile_hint >= 1 && p.tile_hint <= 4) || p.tile_hint == 6) return p.tile_hint;
+    for (const int id : {g_tile, p.tile_hint}) {  // a forced or hinted id of this kernel (gemm_tiles.cuh)
+        const Tile* t = find_tile(id);
+        if (t && t->loop == 4) return id;
+    }
     const int64_t b128 = (int64_t)((p.M + 127) / 128) * ((p.N + 127) / 128);
     if (conv) return 3;  // 64 x 128 wins for every conv shape of the UNet (r01_b probe: 339 / 540 / 570 TF at 32^2 / 64^2 / 128^2)
     if (p.geglu) return 1;
@@ -742,11 +745,11 @@ int launch_stages(const GemmP& p, int stages, hipStream_t stream) {
 template <typename T, bool CONV>
 int launch_tile(const GemmP& p, hipStream_t stream) {
     int tile = pick_tile(p, CONV);
-    if (p.geglu && (tile == 2 || tile == 4)) tile = 3;  // the GEGLU epilogue needs 64 packed columns per wave
-    if (p.colstats && tile == 6) tile = 1;               // column statistics come from the 4-wave tiles' epilogue (whoever asked for tile 6: hint, table or set_option)
+    if (p.geglu && find_tile(tile)->bn < 128) tile = 3;  // the GEGLU epilogue needs 64 packed columns per wave
+    if (p.colstats && find_tile(tile)->kgroups > 1) tile = find_tile(tile)->fallback;  // column statistics come from the 4-wave tiles' epilogue (whoever asked for tile 6: hint, table or set_option)
     const int st = pick_stages(p);
     if (p.lora_b) {  // in-launch LoRA: the 4-wave tiles, two LDS stages; a stacked rank above 64 needs the 128-column tiles (the producers stage R weight rows)
-        if (p.lora_r > 64 && (tile == 2 || tile == 4)) tile = tile == 2 ? 1 : 3;
+        if (p.lora_r > 64 && find_tile(tile)->bn < 128) tile = find_tile(tile)->bm == 128 ? 1 : 3;
         if constexpr (CONV) {
             return tile == 1 ? launch_cfg<T, 128, 128, 2, 2, true, 2, 1, true>(p, stream) : launch_cfg<T, 64, 128, 2, 2, true, 2, 1, true>(p, stream);
         } else {
@@ -758,17 +761,17 @@ int launch_tile(const GemmP& p, hipStream_t stream) {
             }
         }
     }
-#ifdef MI355X_PROBE_T10  // (probing build, round 6: 128 x 96 tiles computed by four waves stacked along M -- wave tile 32 x 96 -- for plain launches: does the layout that a
+#ifdef MI355X_PROBE_T10  // (probing build, round 6, ids 20 .. 25 -- never an id of gemm_tiles.cuh: 128 x 96 tiles computed by four waves stacked along M -- wave tile 32 x 96 -- for plain launches: does the layout that a
                          //  256-workgroup tile of N = 1280 (128 x 80) would need hold up against 64 x 64 tiles?  tools/probe_t10.py)
     if constexpr (!CONV) {
-        if (g_tile == 10 || p.tile_hint == 10) return launch_cfg<T, 128, 96, 4, 1, false, 2>(p, stream);
-        if (g_tile == 11 || p.tile_hint == 11) return launch_cfg<T, 128, 96, 4, 1, false, 3>(p, stream);
+        if (g_tile == 20 || p.tile_hint == 20) return launch_cfg<T, 128, 96, 4, 1, false, 2>(p, stream);
+        if (g_tile == 21 || p.tile_hint == 21) return launch_cfg<T, 128, 96, 4, 1, false, 3>(p, stream);
         // TWO-wave workgroups (128 threads): fewer LDS fragment reads per MFMA at the same tile -- 64 x 64 as 2 x (32 x 64): 0.75 instead of 1.0;
         // 128 x 64 as 2 x (64 x 64): 0.5 instead of 0.75 -- and more workgroups per CU for the same LDS
-        if (g_tile == 12 || p.tile_hint == 12) return launch_cfg<T, 64, 64, 2, 1, false, 2>(p, stream);
-        if (g_tile == 13 || p.tile_hint == 13) return launch_cfg<T, 64, 64, 2, 1, false, 3>(p, stream);
-        if (g_tile == 14 || p.tile_hint == 14) return launch_cfg<T, 128, 64, 2, 1, false, 2>(p, stream);
-        if (g_tile == 15 || p.tile_hint == 15) return launch_cfg<T, 128, 64, 2, 1, false, 3>(p, stream);
+        if (g_tile == 22 || p.tile_hint == 22) return launch_cfg<T, 64, 64, 2, 1, false, 2>(p, stream);
+        if (g_tile == 23 || p.tile_hint == 23) return launch_cfg<T, 64, 64, 2, 1, false, 3>(p, stream);
+        if (g_tile == 24 || p.tile_hint == 24) return launch_cfg<T, 128, 64, 2, 1, false, 2>(p, stream);
+        if (g_tile == 25 || p.tile_hint == 25) return launch_cfg<T, 128, 64, 2, 1, false, 3>(p, stream);
     }
 #endif
     switch (tile) {

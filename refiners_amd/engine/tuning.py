@@ -13,6 +13,8 @@ import os
 from pathlib import Path
 from typing import Optional
 
+from . import tiles
+
 TABLE_PATH = Path(__file__).resolve().parent / "tuning_gfx950.json"
 _table: Optional[dict] = None
 enabled = os.environ.get("REFINERS_AMD_TUNING", "1") != "0"
@@ -41,13 +43,11 @@ def lookup(signature: str, stages: int = 0) -> tuple[int, int]:
         got = table().get(signature)
         if got is None and signature.endswith("lora"):  # the LoRA producers leave the tiles' K loop untouched: same choice as the un-adapted launch
             got = table().get(signature[: -len("lora")])
-            if got is not None and got[0] in (7, 8, 9, 10, 12):
+            if got is not None:
                 # the 8-wave loop takes the LoRAs of a plain one-segment GEMM with one column group (whole tiles: no stream-K); a launch it cannot
-                # take -- several groups, a transposed group, a convolution -- gets the 128 x 128 tile of the 4-wave kernel
+                # take -- several groups, a transposed group, a convolution -- gets the 128 x 128 tile of the 4-wave kernel (tiles.lora_choice)
                 kind, _, _, seg, flags = signature.split(":")
-                got = (9 if got[0] == 9 else 7, 0) if lora_g8 and kind == "gemm" and seg == "s1" and "T" not in flags else (1, 2)
-            elif got is not None and (got[0] > 4 or got[1] != 2):  # the 4-wave LoRA kernels exist for tiles 1 .. 4 with two LDS stages
-                got = (got[0] if got[0] <= 4 else 1, 2)
+                got = tiles.lora_choice(got[0], lora_g8 and tiles.g8_takes_lora(kind, int(seg[1:]), 1, "T" in flags))
         if got is not None:
             return int(got[0]), int(got[1])
     return 0, stages

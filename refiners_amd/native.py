@@ -1069,20 +1069,18 @@ def _fill_split(a: GemmArgs, tile: int, ksplit: int, ws: Optional[Tensor], stage
     """tile / stages / split-K of a launch.  tile == 0 and no split: the measured table of this GPU decides, if it knows the shape.  An EXPLICIT choice
     (tile != 0, or a split) is the caller's and stays (tests and probes of split-K on tabled shapes must run split-K) -- unless the caller says its
     split is only a heuristic (`table_may_replace_split`: Lowering.conv's three-way split for want of tiles): where the table prefers the 8-wave loop
-    (tiles 7 / 8 / 9: whole tiles or stream-K) the launch asks for that tile and KEEPS ksplit / ws: mi355x_gemm drops the split when the 8-wave loop
+    (engine/tiles.py: whole tiles or stream-K) the launch asks for that tile and KEEPS ksplit / ws: mi355x_gemm drops the split when the 8-wave loop
     takes the launch and runs the split on the 128 x 128 tile when it cannot (unaligned operands, 2 GB and more)."""
-    if tile == 0 and ksplit <= 1:
-        from .engine import tuning
+    from .engine import tiles, tuning
 
+    if tile == 0 and ksplit <= 1:
         tile, stages = tuning.lookup(gemm_signature(a), stages)
     elif ksplit > 1 and table_may_replace_split:
-        from .engine import tuning
-
         t8, _ = tuning.lookup(gemm_signature(a), 0)
-        if t8 in (7, 8, 9, 10, 12):
+        if tiles.takes_whole_k(t8):
             tile = t8
     a.tile, a.ksplit, a.stages = tile, ksplit, stages
-    if tile == 8 or os.environ.get("REFINERS_AMD_FORCE_TILE") == "8":
+    if tiles.needs_streamk_scratch(tile) or tiles.needs_streamk_scratch(int(os.environ.get("REFINERS_AMD_FORCE_TILE") or 0)):
         sk = _streamk_current
         if sk is None:
             # eager call (tests, probes): one scratch per (device of the operands, current stream) -- launches on two streams of one device must not

@@ -22,7 +22,7 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 from refiners_amd import native  # noqa: E402
-from refiners_amd.engine import tuning  # noqa: E402
+from refiners_amd.engine import tiles, tuning  # noqa: E402
 
 
 def step_ms(ops, iters: int = 4, reps: int = 3) -> float:
@@ -33,25 +33,17 @@ def step_ms(ops, iters: int = 4, reps: int = 3) -> float:
     return statistics.median(vals)
 
 
+NOT_TUNED = (10, 11)  # (ids the tuner does not propose: not in the measured table)
+
+
 def candidates(a, only=None) -> list[tuple[int, int]]:
+    """Every (tile, LDS depth) of engine/tiles.py that takes the launch and is a configuration of its own for it (with LoRA the stream-K id runs as whole tiles)."""
     out = []
-    if not a.lora_b and not (a.out_t and a.nt_begin % 256):  # the 8-wave / eight-phase loop: 7 = whole 256 x 256 tiles, 8 = stream-K, 9 = whole 192 x 256 tiles
-        out += [(7, 0), (8, 0)] + ([] if a.out_t else [(9, 0)])
-    elif a.lora_b and not a.conv and a.lora_groups == 1 and a.nseg == 1 and not a.out_t:  # its in-launch LoRA: one column group of a plain GEMM, whole tiles
-        out += [(7, 0), (9, 0)]
-    if a.dtype != 0 and not (a.lora_b or a.out_t or a.geglu == 1 or a.ln_stats or a.stats_out or a.out_f32):  # 12 = whole 128 x 320 tiles of the same loop
-        out.append((12, 0))
-    if a.ksplit > 1:  # a launch the lowering split along K: only the 8-wave loop (which takes the whole K) is an alternative
-        return [c for c in out if only is None or c[0] in only]
-    for tile in (1, 2, 3, 4, 6):  # 128x128, 128x64, 64x128, 64x64 (4 waves); 6 = 128x128 with two K groups (8 waves)
-        if a.geglu == 1 and tile in (2, 4):
-            continue
-        if a.lora_b and tile == 6:  # in-launch LoRA exists for the 4-wave tiles only, with two LDS stages
-            continue
-        if a.lora_b and a.lora_r > 64 and tile in (2, 4):  # a stacked rank above 64 needs the 128-column tiles
-            continue
-        for st in ((2,) if tile == 6 or a.lora_b else (2, 3, 4)):
-            out.append((tile, st))
+    rows = [t for t in tiles.TILES if t.id not in NOT_TUNED and tiles.takes(t, a) and not (a.lora_b and t.lora_to != t.id)]
+    for t in [t for t in rows if t.loop == 8]:  # the 8-wave / eight-phase loop first
+        out.append((t.id, 0))
+    for t in [t for t in rows if t.loop == 4 and a.ksplit <= 1]:  # a launch the lowering split along K: only the 8-wave loop (which takes the whole K) is an alternative
+        out += [(t.id, st) for st in ((2,) if a.lora_b else range(t.st_lo, t.st_hi + 1))]  # (the 4-wave LoRA kernels have two LDS stages)
     return [c for c in out if only is None or c[0] in only]
 
 
@@ -136,8 +128,8 @@ def main() -> None:
         def apply(tile, st):
             for a in items:
                 a.tile, a.stages = tile, st
-                a.ksplit = 1 if tile in (7, 8, 9, 12) else ks0
-                if tile == 8:
+                a.ksplit = 1 if tiles.takes_whole_k(tile) else ks0
+                if tiles.needs_streamk_scratch(tile):
                     native.attach_streamk(a, low._sk)
 
         for tile, st in [(0, 0)] + candidates(a0, only):

@@ -27,10 +27,13 @@ import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+from refiners_amd.engine import tiles as tile_table  # noqa: E402  (no torch behind it)
+
 CSRC = ROOT / "refiners_amd" / "csrc"
-TILES = {1: (128, 128), 2: (128, 64), 3: (64, 128), 4: (64, 64), 6: (128, 128)}
+TILES = {t.id: t for t in tile_table.TILES if t.loop == 4}
 CUS, LDS_CU, VGPR_SIMD = 256, 160 * 1024, 512
-G8_TILES = {7: (256, 256), 8: (256, 256), 9: (192, 256)}  # 8 = stream-K over the same tiles (every CU gets an equal share of (tiles x K tiles): balance 1 by construction)
+G8_TILES = {t.id: t for t in tile_table.TILES if t.loop == 8}  # stream-K: every CU gets an equal share of (tiles x K tiles), balance 1 by construction
 
 
 def kernel_resources(cache: Path) -> dict:
@@ -83,22 +86,21 @@ def analyse(cls: str, res: dict) -> dict | None:
         tuned = True
     if tile == 0:
         tile = pick_tile(M, N, conv, geglu)
-    if geglu and tile in (2, 4):
+    if geglu and tile in TILES and TILES[tile].bn < 128:
         tile = 3
     if lora:
         stages = 2
         if conv and tile not in (1, 3):
             tile = 3
     if tile in G8_TILES:  # the 8-wave loop (csrc/gemm8_kernel.cuh): one workgroup per CU by construction (256 registers x 8 waves, 122-138 KB of LDS); its in-launch LoRA has t-tiles
-        BM, BN = G8_TILES[tile]
+        BM, BN, sk = G8_TILES[tile].bm, G8_TILES[tile].bn, G8_TILES[tile].streamk
         tiles = -(-M // BM) * -(-N // BN)
         head, kind = (-(-(-(-M // BM)) // 8) * 8, "t-tiles") if lora else (0, "")
         rounds = (tiles + head) / CUS
-        return {"class": cls, "tile": f"{BM}x{BN}" + ("*" if tuned else "") + (" stream-K" if tile == 8 else ""), "stages": 2, "vgpr": 256 if tile != 9 else 224, "lds_kb": round((2 * (BM + BN) * 128 + 10240) / 1024, 1),
+        return {"class": cls, "tile": f"{BM}x{BN}" + ("*" if tuned else "") + (" stream-K" if sk else ""), "stages": 2, "vgpr": 256 if tile != 9 else 224, "lds_kb": round((2 * (BM + BN) * 128 + 10240) / 1024, 1),
                 "per_cu": 1, "tiles": tiles, "head": head, "head_kind": kind, "slots": CUS, "rounds": round(rounds, 3), "tiles_per_cu": tiles / CUS,
-                "balance": 1.0 if tile == 8 else tiles / CUS / math.ceil(tiles / CUS)}
-    BM, BN = TILES[tile]
-    KG = 2 if tile == 6 else 1
+                "balance": 1.0 if sk else tiles / CUS / math.ceil(tiles / CUS)}
+    BM, BN, KG = TILES[tile].bm, TILES[tile].bn, TILES[tile].kgroups
     key = f"{dt},{BM},{BN},{int(conv)},{stages},{KG},{int(lora)}"
     r = res.get(key)
     if r is None:

@@ -8,6 +8,7 @@ sys.path.insert(0, str(ROOT))
 import torch  # noqa: E402
 
 from refiners_amd import native  # noqa: E402
+from refiners_amd.engine import tiles  # noqa: E402
 
 dev = "cuda"
 dt = torch.bfloat16
@@ -42,8 +43,8 @@ def main():
         w = (torch.randn(N, K, device=dev) * K ** -0.5).to(dt)
         o = torch.empty(M, N // 2 if geglu else N, device=dev, dtype=dt)
         best = None
-        for tile in (1, 2, 3, 4, 6):
-            if geglu and tile in (2, 4):
+        for tile in tiles.IDS_4WAVE:
+            if geglu and tiles.BY_ID[tile].bn < 128:  # (the GEGLU epilogue needs the 128-column tiles)
                 continue
             line = f"gemm M={M:5d} K={K:5d} N={N:5d} geglu={int(geglu)} tile={tile}:"
             for st in (2, 3):
