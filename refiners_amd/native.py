@@ -4,6 +4,10 @@ This module is the ONLY place where Python touches the native library.  It delib
 device pointers, sizes, strides and scalars; torch is used as the owner of device memory and of the current HIP
 stream.  There is no CPU or PyTorch fallback here: if the library is missing or a kernel refuses a shape, the call
 raises `NativeError` (the fused fluxion nodes decide, *before* calling, whether a sub-tree is eligible).
+
+The header is the only description of the ABI: the argument structs (GemmArgs, AttnArgs, ...), the prototypes `load()` sets and the
+scalar constants are read from it at import by refiners_amd.abi, nothing of it is restated here.  What this module adds is the
+Python name of each struct (STRUCT_NAMES), the probing entry points the header leaves out on purpose (UNSTABLE), and the wrappers.
 """
 from __future__ import annotations
 
@@ -16,34 +20,61 @@ from typing import Any, Optional, Sequence
 import torch
 from torch import Tensor
 
-MI355X_F32 = 0
-MI355X_BF16 = 1
-MAX_SEG = 3
+from . import abi
 
-_ERR = {0: "OK", -1: "EDTYPE", -2: "ESHAPE", -3: "ELAUNCH", -4: "EARG"}
+#: C struct of the header -> the name its ctypes.Structure class has in this module (a header struct that is missing here is an import error)
+STRUCT_NAMES = {
+    "mi355x_gemm_seg": "GemmSeg",
+    "mi355x_gemm_args": "GemmArgs",
+    "mi355x_kv_stream": "KvStream",
+    "mi355x_attn_args": "AttnArgs",
+    "mi355x_attn_general_args": "AttnGeneralArgs",
+    "mi355x_layernorm_args": "LayerNormArgs",
+    "mi355x_groupnorm_args": "GroupNormArgs",
+    "mi355x_sam_attn_args": "SamAttnArgs",
+    "mi355x_sam_mask_head_args": "SamMaskHeadArgs",
+    "mi355x_sam_postprocess_args": "SamPostprocessArgs",  # its field `in` is `in_` here
+    "mi355x_adain_stats_args": "AdainStatsArgs",
+    "mi355x_style_aligned_args": "StyleAlignedArgs",
+    "mi355x_md_gather_desc": "MdGatherDesc",
+    "mi355x_md_gather_args": "MdGatherArgs",
+    "mi355x_md_step_args": "MdStepArgs",
+    "mi355x_md_blend_desc": "MdBlendDesc",
+    "mi355x_md_blend_args": "MdBlendArgs",
+    "mi355x_groupnorm_table_args": "GroupNormTableArgs",
+    "mi355x_groupnorm_fixed_args": "GroupNormFixedArgs",
+    "mi355x_vae_tile_pos": "VaeTilePos",
+    "mi355x_vae_gather_args": "VaeGatherArgs",
+    "mi355x_vae_axis": "VaeAxis",
+    "mi355x_vae_blend_tile": "VaeBlendTile",
+    "mi355x_vae_blend_args": "VaeBlendArgs",
+}
+_abi = abi.read(STRUCT_NAMES)
+globals().update({cls.__name__: cls for cls in _abi.structs.values()})  # GemmSeg ... VaeBlendArgs: real ctypes.Structure subclasses
+_K = _abi.constants
+
+#: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
+EXPORTS = list(_abi.functions)
+#: exported for probing and A/B runs, by design not in the header (no stable contract): name -> (restype, argtypes), applied by load() like the header's
+UNSTABLE = {
+    "mi355x_set_option": (C.c_int, [C.c_char_p, C.c_int]),
+    "mi355x_get_stat": (C.c_int, [C.c_char_p]),
+    "mi355x_attention_set_glds": (C.c_int, [C.c_int]),
+    "mi355x_attention_set_nw": (C.c_int, [C.c_int]),
+    "mi355x_attention_set_pipeline": (C.c_int, [C.c_int, C.c_int]),
+    "mi355x_attention_general_set_fast": (C.c_int, [C.c_int]),
+}
+
+ABI_VERSION = _K["MI355X_ABI_VERSION"]
+MI355X_F32, MI355X_BF16 = _K["MI355X_F32"], _K["MI355X_BF16"]
+MAX_SEG, MAX_PREFETCH = _K["MI355X_MAX_SEG"], _K["MI355X_MAX_PREFETCH"]
+_ERR = {v: k[len("MI355X_"):] for k, v in next(e for e in _abi.enums if "MI355X_OK" in e).items()}  # 0: "OK", -1: "EDTYPE", ...
 
 LIB_PATH = Path(__file__).resolve().parent / "csrc" / "libmi355x_refiners.so"
 
 
 class NativeError(RuntimeError):
     """Raised when the native library is unavailable or a native call returns a negative status."""
-
-
-class GemmSeg(C.Structure):
-    _fields_ = [
-        ("x", C.c_void_p),
-        ("ldx", C.c_int64),
-        ("w", C.c_void_p),
-        ("ldw", C.c_int64),
-        ("k", C.c_int32),
-        ("ksize", C.c_int32),
-        ("stride", C.c_int32),
-        ("ups", C.c_int32),
-        ("H", C.c_int32),
-        ("W", C.c_int32),
-        ("asym", C.c_int32),
-        ("kblocked", C.c_int32),
-    ]
 
 
 class KBlocked:
@@ -91,7 +122,6 @@ class KBlocked:
         return self.t.device
 
 
-MAX_PREFETCH = 2  # == MI355X_MAX_PREFETCH
 LORA_R = 32  # granularity of the stacked LoRA rank mi355x_gemm handles inside the parent launch (gemm_kernel.cuh: LORA_RC)
 LORA_RMAX = 128  # largest stacked rank (LORA_RMAX there)
 
@@ -100,330 +130,6 @@ def lora_rank(rt: int) -> int:
     """Stacked rank -> the padded rank the kernel handles (32, 64 or 128); 0 = too large for the in-launch path."""
     return next((r for r in (32, 64, 128) if rt <= r), 0)
 
-
-class GemmArgs(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32),
-        ("M", C.c_int32),
-        ("N", C.c_int32),
-        ("nseg", C.c_int32),
-        ("conv", C.c_int32),
-        ("B", C.c_int32),
-        ("OH", C.c_int32),
-        ("OW", C.c_int32),
-        ("seg", GemmSeg * MAX_SEG),
-        ("out", C.c_void_p),
-        ("ldo", C.c_int64),
-        ("bias", C.c_void_p),
-        ("rowbias", C.c_void_p),
-        ("ld_rowbias", C.c_int64),
-        ("rows_per_group", C.c_int32),
-        ("geglu", C.c_int32),
-        ("res", C.c_void_p),
-        ("ldres", C.c_int64),
-        ("zeros", C.c_void_p),
-        ("tile", C.c_int32),
-        ("ksplit", C.c_int32),
-        ("ws", C.c_void_p),
-        ("ws_bytes", C.c_int64),
-        ("prefetch", C.c_void_p * MAX_PREFETCH),
-        ("prefetch_bytes", C.c_int64 * MAX_PREFETCH),
-        ("prefetch_blocks", C.c_int32),
-        ("out_kblocked", C.c_int32),
-        ("stages", C.c_int32),
-        ("nt_begin", C.c_int32),
-        ("out_t", C.c_void_p),
-        ("ldt", C.c_int64),
-        ("ln_stats", C.c_void_p),
-        ("ln_parts", C.c_int32),
-        ("ln_eps", C.c_float),
-        ("ln_s", C.c_void_p),
-        ("ln_c", C.c_void_p),
-        ("stats_out", C.c_void_p),
-        ("out_f32", C.c_int32),
-        ("lora_a", C.c_void_p * 3),
-        ("lora_nb", C.c_int32 * 3),
-        ("lora_groups", C.c_int32),
-        ("lora_r", C.c_int32),
-        ("lora_b", C.c_void_p),
-        ("lora_ls", C.c_void_p),
-        ("lora_lc", C.c_void_p),
-        ("lora_t", C.c_void_p),
-        ("lora_flags", C.c_void_p),
-        ("lora_epoch", C.c_void_p),
-        ("colstats_out", C.c_void_p),
-        ("sk_ws", C.c_void_p),
-        ("sk_flags", C.c_void_p),
-        ("sk_slots", C.c_int32),
-    ]
-
-
-class KvStream(C.Structure):
-    _fields_ = [
-        ("k", C.c_void_p),
-        ("ldk", C.c_int64),
-        ("k_batch_stride", C.c_int64),
-        ("vt", C.c_void_p),
-        ("ldvt", C.c_int64),
-        ("vt_batch_stride", C.c_int64),
-        ("Lk", C.c_int32),
-        ("out_scale", C.c_float),
-    ]
-
-
-class AttnArgs(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32),
-        ("B", C.c_int32),
-        ("H", C.c_int32),
-        ("D", C.c_int32),
-        ("Lq", C.c_int32),
-        ("nstream", C.c_int32),
-        ("q", C.c_void_p),
-        ("ldq", C.c_int64),
-        ("q_batch_stride", C.c_int64),
-        ("out", C.c_void_p),
-        ("ldo", C.c_int64),
-        ("o_batch_stride", C.c_int64),
-        ("scale", C.c_float),
-        ("kv", KvStream * 2),
-    ]
-
-
-class AttnGeneralArgs(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32),
-        ("B", C.c_int32),
-        ("H", C.c_int32),
-        ("Lq", C.c_int32),
-        ("Lk", C.c_int32),
-        ("Dqk", C.c_int32),
-        ("Dv", C.c_int32),
-        ("causal", C.c_int32),
-        ("q", C.c_void_p),
-        ("ldq", C.c_int64),
-        ("q_batch_stride", C.c_int64),
-        ("k", C.c_void_p),
-        ("ldk", C.c_int64),
-        ("k_batch_stride", C.c_int64),
-        ("vt", C.c_void_p),
-        ("ldvt", C.c_int64),
-        ("vt_batch_stride", C.c_int64),
-        ("out", C.c_void_p),
-        ("ldo", C.c_int64),
-        ("o_batch_stride", C.c_int64),
-        ("scale", C.c_float),
-        ("out_scale", C.c_float),
-    ]
-
-
-class LayerNormArgs(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32),
-        ("M", C.c_int32),
-        ("C", C.c_int32),
-        ("x", C.c_void_p),
-        ("ldx", C.c_int64),
-        ("gamma", C.c_void_p),
-        ("beta", C.c_void_p),
-        ("eps", C.c_float),
-        ("out", C.c_void_p),
-        ("ldo", C.c_int64),
-    ]
-
-
-class GroupNormArgs(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32),
-        ("B", C.c_int32),
-        ("HW", C.c_int32),
-        ("C", C.c_int32),
-        ("G", C.c_int32),
-        ("x", C.c_void_p),
-        ("ldx", C.c_int64),
-        ("gamma", C.c_void_p),
-        ("beta", C.c_void_p),
-        ("eps", C.c_float),
-        ("silu", C.c_int32),
-        ("out", C.c_void_p),
-        ("ldo", C.c_int64),
-        ("ws", C.c_void_p),
-        ("colstats", C.c_void_p),
-        ("x2", C.c_void_p),
-        ("ldx2", C.c_int64),
-        ("C1", C.c_int32),
-        ("colstats2", C.c_void_p),
-    ]
-
-
-
-class SamAttnArgs(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("D", C.c_int32), ("Lq", C.c_int32), ("Lk", C.c_int32),
-        ("q", C.c_void_p), ("ldq", C.c_int64), ("q_batch_stride", C.c_int64),
-        ("k", C.c_void_p), ("ldk", C.c_int64), ("k_batch_stride", C.c_int64),
-        ("v", C.c_void_p), ("ldv", C.c_int64), ("v_batch_stride", C.c_int64),
-        ("out", C.c_void_p), ("ldo", C.c_int64), ("o_batch_stride", C.c_int64),
-        ("scale", C.c_float), ("ws", C.c_void_p), ("ws_floats", C.c_int64),
-    ]
-
-
-class SamMaskHeadArgs(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32), ("P", C.c_int32), ("Hin", C.c_int32), ("Win", C.c_int32), ("nk", C.c_int32),
-        ("x", C.c_void_p), ("ldx", C.c_int64), ("w", C.c_void_p), ("bias", C.c_void_p),
-        ("hyper", C.c_void_p), ("ld_hyper", C.c_int64), ("hyper_batch_stride", C.c_int64),
-        ("out", C.c_void_p), ("out_batch_stride", C.c_int64),
-    ]
-
-
-class SamPostprocessArgs(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32), ("N", C.c_int32), ("Hin", C.c_int32), ("Win", C.c_int32), ("R", C.c_int32), ("sh", C.c_int32), ("sw", C.c_int32),
-        ("H", C.c_int32), ("W", C.c_int32), ("in_", C.c_void_p), ("in_plane_stride", C.c_int64), ("out", C.c_void_p),
-        ("binarize", C.c_int32), ("threshold", C.c_float),
-    ]
-
-
-class AdainStatsArgs(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32), ("B", C.c_int32), ("L", C.c_int32), ("C", C.c_int32),
-        ("x", C.c_void_p), ("ldx", C.c_int64), ("x_batch_stride", C.c_int64),
-        ("stats", C.c_void_p), ("ws", C.c_void_p), ("ws_floats", C.c_int64),
-    ]
-
-
-class StyleAlignedArgs(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32), ("B", C.c_int32), ("L", C.c_int32), ("C", C.c_int32), ("n", C.c_int32),
-        ("q", C.c_void_p), ("ldq", C.c_int64), ("q_batch_stride", C.c_int64),
-        ("k", C.c_void_p), ("ldk", C.c_int64), ("k_batch_stride", C.c_int64),
-        ("vt", C.c_void_p), ("ldvt", C.c_int64), ("vt_batch_stride", C.c_int64),
-        ("q_stats", C.c_void_p), ("k_stats", C.c_void_p), ("stats_batch_stride", C.c_int64),
-        ("scale", C.c_void_p), ("eps", C.c_float),
-        ("k_sh", C.c_void_p), ("ld_ksh", C.c_int64), ("ksh_batch_stride", C.c_int64),
-        ("vt_sh", C.c_void_p), ("ld_vtsh", C.c_int64), ("vtsh_batch_stride", C.c_int64),
-    ]
-
-
-class MdGatherDesc(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("top", C.c_int32), ("left", C.c_int32), ("init_row", C.c_int32), ("a", C.c_float), ("b", C.c_float), ("s", C.c_float), ("reserved", C.c_int32)]
-
-
-class MdGatherArgs(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32), ("T", C.c_int32), ("C", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_init", C.c_int32),
-        ("canvas", C.c_void_p), ("noise", C.c_void_p), ("init", C.c_void_p), ("desc", C.c_void_p), ("desc_host", C.c_void_p), ("view", C.c_void_p), ("model_in", C.c_void_p),
-    ]
-
-
-class MdStepArgs(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32), ("form", C.c_int32), ("T", C.c_int32), ("n", C.c_int64),
-        ("view", C.c_void_p), ("unet_out", C.c_void_p), ("stepped", C.c_void_p), ("hist", C.c_void_p), ("coef", C.c_void_p),
-    ]
-
-
-class MdBlendDesc(C.Structure):
-    _fields_ = [
-        ("top", C.c_int32), ("left", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("weight", C.c_float), ("reserved", C.c_int32), ("stepped_off", C.c_int64),
-        ("mask", C.c_void_p), ("mask_sc", C.c_int64), ("mask_sh", C.c_int64), ("mask_sw", C.c_int64),
-    ]
-
-
-class MdBlendArgs(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32), ("n_targets", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
-        ("canvas", C.c_void_p), ("stepped", C.c_void_p), ("stepped_elems", C.c_int64), ("desc", C.c_void_p), ("desc_host", C.c_void_p),
-    ]
-
-
-class GroupNormTableArgs(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32), ("B", C.c_int32), ("HW", C.c_int32), ("C", C.c_int32), ("G", C.c_int32),
-        ("x", C.c_void_p), ("ldx", C.c_int64), ("gamma", C.c_void_p), ("eps", C.c_float), ("reserved", C.c_int32),
-        ("ws", C.c_void_p), ("tab", C.c_void_p), ("raw", C.c_void_p),
-    ]
-
-
-class GroupNormFixedArgs(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32), ("B", C.c_int32), ("HW", C.c_int32), ("C", C.c_int32), ("silu", C.c_int32), ("reserved", C.c_int32),
-        ("x", C.c_void_p), ("ldx", C.c_int64), ("tab", C.c_void_p), ("beta", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_int64),
-    ]
-
-
-class VaeTilePos(C.Structure):
-    _fields_ = [("top", C.c_int32), ("left", C.c_int32)]
-
-
-class VaeGatherArgs(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32), ("T", C.c_int32), ("C", C.c_int32), ("cpad", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
-        ("canvas", C.c_void_p), ("pos", C.c_void_p), ("pos_host", C.c_void_p), ("dst", C.c_void_p), ("dst_elems", C.c_int64),
-        ("s_tile", C.c_int64), ("s_c", C.c_int64), ("s_y", C.c_int64), ("s_x", C.c_int64),
-    ]
-
-
-class VaeAxis(C.Structure):
-    _fields_ = [("start", C.c_int32), ("extent", C.c_int32)]
-
-
-class VaeBlendTile(C.Structure):
-    _fields_ = [("off", C.c_int64), ("s_c", C.c_int64), ("s_y", C.c_int64), ("s_x", C.c_int64), ("ramp_off", C.c_int32), ("ramp_len", C.c_int32)]
-
-
-class VaeBlendArgs(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
-        ("nx", C.c_int32), ("ny", C.c_int32), ("stride_x", C.c_int32), ("stride_y", C.c_int32), ("tile_w", C.c_int32), ("tile_h", C.c_int32),
-        ("canvas", C.c_void_p), ("src", C.c_void_p), ("src_elems", C.c_int64), ("ramps", C.c_void_p), ("ramp_elems", C.c_int64),
-        ("axis", C.c_void_p), ("axis_host", C.c_void_p), ("tiles", C.c_void_p), ("tiles_host", C.c_void_p),
-    ]
-
-
-#: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
-EXPORTS = [
-    "mi355x_abi_version",
-    "mi355x_device_info",
-    "mi355x_gemm",
-    "mi355x_epoch_bump",
-    "mi355x_attention",
-    "mi355x_attention_general",
-    "mi355x_layernorm",
-    "mi355x_groupnorm_ws_floats",
-    "mi355x_groupnorm",
-    "mi355x_nchw_to_nhwc",
-    "mi355x_nhwc_to_nchw",
-    "mi355x_im2col3x3_nchw",
-    "mi355x_concat2",
-    "mi355x_axpby",
-    "mi355x_silu",
-    "mi355x_softmax_rows",
-    "mi355x_colsum_rows",
-    "mi355x_sag_degrade",
-    "mi355x_cfg_ddim_step",
-    "mi355x_cfg_linear_step",
-    "mi355x_sinusoidal",
-    "mi355x_patchify_nchw",
-    "mi355x_gather_rows",
-    "mi355x_pointwise_nchw",
-    "mi355x_relpos_pack",
-    "mi355x_sam_attention",
-    "mi355x_convt2x2_ln_gelu",
-    "mi355x_sam_mask_head",
-    "mi355x_sam_postprocess_masks",
-    "mi355x_adain_stats_ws_floats",
-    "mi355x_adain_stats",
-    "mi355x_style_aligned_pack",
-    "mi355x_md_gather",
-    "mi355x_md_target_step",
-    "mi355x_md_blend",
-    "mi355x_groupnorm_table",
-    "mi355x_groupnorm_fixed",
-    "mi355x_vae_tile_gather",
-    "mi355x_vae_tile_blend",
-]
 
 _lib: Optional[C.CDLL] = None
 _lib_path: Optional[str] = None
@@ -444,57 +150,13 @@ def load(path: Optional[Path] = None) -> C.CDLL:
         lib = C.CDLL(str(p))
     except OSError as e:  # e.g. no HIP runtime on this machine
         raise NativeError(f"cannot load {p}: {e}") from e
-    lib.mi355x_abi_version.restype = C.c_int
+    for name, (restype, argtypes) in {**_abi.functions, **UNSTABLE}.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    if lib.mi355x_abi_version() != ABI_VERSION:
+        raise NativeError("libmi355x_refiners.so ABI version mismatch")
     if os.environ.get("REFINERS_AMD_FORCE_TILE"):  # probing: every GEMM / conv launch that can run on this tile configuration does (tools, A/B runs)
         lib.mi355x_set_option(b"tile", int(os.environ["REFINERS_AMD_FORCE_TILE"]))
-    lib.mi355x_device_info.argtypes = [C.c_char_p, C.c_int32]
-    lib.mi355x_gemm.argtypes = [C.POINTER(GemmArgs), C.c_void_p]
-    lib.mi355x_epoch_bump.argtypes = [C.c_void_p, C.c_void_p]
-    lib.mi355x_attention.argtypes = [C.POINTER(AttnArgs), C.c_void_p]
-    lib.mi355x_attention_general.argtypes = [C.POINTER(AttnGeneralArgs), C.c_void_p]
-    lib.mi355x_layernorm.argtypes = [C.POINTER(LayerNormArgs), C.c_void_p]
-    lib.mi355x_groupnorm.argtypes = [C.POINTER(GroupNormArgs), C.c_void_p]
-    lib.mi355x_groupnorm_ws_floats.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.mi355x_groupnorm_ws_floats.restype = C.c_int64
-    lib.mi355x_nchw_to_nhwc.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]
-    lib.mi355x_nhwc_to_nchw.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]
-    lib.mi355x_im2col3x3_nchw.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]
-    lib.mi355x_concat2.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
-    lib.mi355x_axpby.argtypes = [C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]
-    lib.mi355x_silu.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    lib.mi355x_colsum_rows.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_void_p]
-    lib.mi355x_sag_degrade.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                       C.c_int32, C.c_int32, C.c_void_p]
-    lib.mi355x_softmax_rows.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
-    lib.mi355x_cfg_ddim_step.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    lib.mi355x_cfg_linear_step.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    lib.mi355x_sinusoidal.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
-    lib.mi355x_patchify_nchw.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]
-    lib.mi355x_gather_rows.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
-    lib.mi355x_pointwise_nchw.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]
-    lib.mi355x_relpos_pack.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    lib.mi355x_sam_attention.argtypes = [C.POINTER(SamAttnArgs), C.c_void_p]
-    lib.mi355x_convt2x2_ln_gelu.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
-                                            C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
-    lib.mi355x_sam_mask_head.argtypes = [C.POINTER(SamMaskHeadArgs), C.c_void_p]
-    lib.mi355x_sam_postprocess_masks.argtypes = [C.POINTER(SamPostprocessArgs), C.c_void_p]
-    lib.mi355x_adain_stats_ws_floats.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.mi355x_adain_stats_ws_floats.restype = C.c_int64
-    lib.mi355x_adain_stats.argtypes = [C.POINTER(AdainStatsArgs), C.c_void_p]
-    lib.mi355x_style_aligned_pack.argtypes = [C.POINTER(StyleAlignedArgs), C.c_void_p]
-    lib.mi355x_md_gather.argtypes = [C.POINTER(MdGatherArgs), C.c_void_p]
-    lib.mi355x_md_target_step.argtypes = [C.POINTER(MdStepArgs), C.c_void_p]
-    lib.mi355x_md_blend.argtypes = [C.POINTER(MdBlendArgs), C.c_void_p]
-    lib.mi355x_groupnorm_table.argtypes = [C.POINTER(GroupNormTableArgs), C.c_void_p]
-    lib.mi355x_groupnorm_fixed.argtypes = [C.POINTER(GroupNormFixedArgs), C.c_void_p]
-    lib.mi355x_vae_tile_gather.argtypes = [C.POINTER(VaeGatherArgs), C.c_void_p]
-    lib.mi355x_vae_tile_blend.argtypes = [C.POINTER(VaeBlendArgs), C.c_void_p]
-    lib.mi355x_set_option.argtypes = [C.c_char_p, C.c_int]
-    lib.mi355x_attention_set_glds.argtypes = [C.c_int]
-    lib.mi355x_attention_general_set_fast.argtypes = [C.c_int]
-    lib.mi355x_attention_set_pipeline.argtypes = [C.c_int, C.c_int]
-    if lib.mi355x_abi_version() != 7:
-        raise NativeError("libmi355x_refiners.so ABI version mismatch")
     _lib = lib
     _lib_path = str(p)
     attention_pipeline_from_env()
@@ -1486,8 +1148,8 @@ def style_aligned_pack(q: Tensor, k: Tensor, vt: Tensor, q_stats: Tensor, k_stat
 
 
 # ------------------------------------------------------------------------------------------------ MultiDiffusion (csrc/multi_diffusion.hip)
-MD_MAX_TARGETS = 64
-MD_SRC_CANVAS, MD_SRC_INIT = 0, 1
+MD_MAX_TARGETS = _K["MI355X_MD_MAX_TARGETS"]
+MD_SRC_CANVAS, MD_SRC_INIT = _K["MI355X_MD_SRC_CANVAS"], _K["MI355X_MD_SRC_INIT"]
 MD_GATHER_DESC_BYTES, MD_BLEND_DESC_BYTES = C.sizeof(MdGatherDesc), C.sizeof(MdBlendDesc)
 
 
@@ -1546,7 +1208,7 @@ def md_target_step(view: Tensor, unet_out: Tensor, stepped: Tensor, hist: Option
     assert unet_out.numel() == 2 * view.numel() and stepped.shape == view.shape and (hist is None or hist.shape == view.shape)
     assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.numel() >= 8 * T and coef.device == view.device
     a = MdStepArgs()
-    a.dtype, a.form, a.T, a.n = dtype_code(view.dtype), 1 if linear else 0, T, view.numel() // T
+    a.dtype, a.form, a.T, a.n = dtype_code(view.dtype), _K["MI355X_MD_FORM_LINEAR" if linear else "MI355X_MD_FORM_DDIM"], T, view.numel() // T
     a.view, a.unet_out, a.stepped, a.hist, a.coef = view.data_ptr(), unet_out.data_ptr(), stepped.data_ptr(), None if hist is None else hist.data_ptr(), coef.data_ptr()
     _launch("mi355x_md_target_step", (C.byref(a),), "mi355x_md_target_step", keep=(a, view, unet_out, stepped, hist, coef))
 
@@ -1566,7 +1228,7 @@ def md_blend(canvas: Tensor, stepped: Tensor, desc: Tensor, desc_host: Tensor, n
 
 # ------------------------------------------------------------------------------------------------ tiled VAE (csrc/norm.hip, csrc/tiled_vae.hip)
 VAE_POS_BYTES, VAE_AXIS_BYTES, VAE_BLEND_TILE_BYTES = C.sizeof(VaeTilePos), C.sizeof(VaeAxis), C.sizeof(VaeBlendTile)
-VAE_MAX_AXIS = 1024
+VAE_MAX_AXIS = _K["MI355X_VAE_MAX_AXIS"]
 
 
 def groupnorm_table(x: Tensor, gamma: Tensor, groups: int, eps: float, tab: Tensor, raw: Optional[Tensor] = None, ws: Optional[Tensor] = None) -> Tensor:

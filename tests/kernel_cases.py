@@ -802,7 +802,6 @@ def with_lora_source(bits, fn):
 def _launch_stat(name: bytes) -> int:
     """mi355x_get_stat: launches since the library was loaded ("g8" = on the 8-wave loop, any tile id; "g8lora" = those with its in-launch LoRA; "g9" = those on 192-row tiles)."""
     lib = native.load()
-    lib.mi355x_get_stat.argtypes = [ctypes.c_char_p]
     return int(lib.mi355x_get_stat(name))
 
 

@@ -5,7 +5,6 @@
 Timed like tools/probe_attn_pipe.py (HIP graph over a rotation of 6 operand sets); the error of every variant is taken against a float32
 softmax(Q K^T / 8) V of the same bf16 operands, on plain normal data and on a set whose scores GROW along the keys (every tile moves the
 running maximum of most queries: the rescale path of the lazy variant)."""
-import ctypes as C
 import sys
 from pathlib import Path
 
@@ -28,7 +27,6 @@ def reference(q, k, vt, H, Lk):
 
 def main():
     lib = native.load()
-    lib.mi355x_attention_set_pipeline.argtypes = [C.c_int, C.c_int]
     dt = torch.bfloat16
     variants = [("opt 1 (round 5)", 1 << 4), ("opt 5 lazy", 5 << 4), ("opt 9 ones", 9 << 4), ("opt 13 lazy+ones", 13 << 4), ("pipelined", (13 << 4) | (1 << 19)),
                 ("pipelined, order free", (13 << 4) | (2 << 19)), ("pipelined, LDS-DMA", (13 << 4) | (3 << 19)), ("  16-query waves", (13 << 4) | (3 << 19) | (3 << 16)), ("  32-query waves", (13 << 4) | (3 << 19) | (1 << 16)),

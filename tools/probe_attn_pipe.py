@@ -3,7 +3,6 @@
 Each configuration is timed over a rotation of 6 independent (q, k, v^T) sets (63-94 MB apiece at the large shapes), so that K / V come
 from the Infinity Cache or HBM as they do in the step, not from a hot L2.
 """
-import ctypes as C
 import sys
 from pathlib import Path
 
@@ -37,7 +36,6 @@ def time_us(fns, n=10, reps=5):
 
 def main():
     lib = native.load()
-    lib.mi355x_attention_set_pipeline.argtypes = [C.c_int, C.c_int]
     dt = torch.bfloat16
     shapes = ((2, 20, 1024, 1024, 0), (2, 10, 4096, 4096, 0), (2, 20, 1024, 77, 4), (2, 10, 4096, 77, 4), (8, 20, 1024, 1024, 0), (8, 10, 4096, 4096, 0))
     for (B, H, Lq, Lk, Lk2) in shapes:

@@ -3,7 +3,6 @@
 Build:  hipcc ... -DMI355X_ATTN_PIPE_ABL=1 attention.hip -> csrc/variants/libmi355x_refiners_pipeabl.so   (tools/build_attn_variant.sh pipeabl MI355X_ATTN_PIPE_ABL=1)
 Run:    REFINERS_AMD_LIB=refiners_amd/csrc/variants/libmi355x_refiners_pipeabl.so python tools/probe_attn_pipe_ablate.py
 """
-import ctypes as C
 import sys
 from pathlib import Path
 
@@ -17,7 +16,6 @@ from tools.probe_attn_pipe import time_us  # noqa: E402
 
 def main():
     lib = native.load()
-    lib.mi355x_attention_set_pipeline.argtypes = [C.c_int, C.c_int]
     dt = torch.bfloat16
     variants = [("attn_kernel opt 13", 13 << 4), ("pipelined", (13 << 4) | (1 << 19)), ("- exponentials", (13 << 4) | (1 << 19) | (1 << 8)), ("- maxima", (13 << 4) | (1 << 19) | (32 << 8)),
                 ("- exponentials - maxima", (13 << 4) | (1 << 19) | (33 << 8)), ("- Q K^T MFMAs", (13 << 4) | (1 << 19) | (2 << 8)), ("- P V MFMAs", (13 << 4) | (1 << 19) | (4 << 8)),

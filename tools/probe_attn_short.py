@@ -1,6 +1,5 @@
 """Cross-attention of the step (77 text keys + 4 image-prompt keys): the short-K/V kernel with 128- and 64-query workgroups (bits 23-24 of the pipeline code:
 1 = 128 always, 2 = 64 always), timed like tools/probe_attn_pipe.py; every variant is compared with the first."""
-import ctypes as C
 import sys
 from pathlib import Path
 
@@ -14,7 +13,6 @@ from tools.probe_attn_pipe import time_us  # noqa: E402
 
 def main():
     lib = native.load()
-    lib.mi355x_attention_set_pipeline.argtypes = [C.c_int, C.c_int]
     dt = torch.bfloat16
     base = 1 | (13 << 4) | (3 << 19)
     variants = [("register-staged, 128-query", base | (1 << 23) | (1 << 25)), ("register-staged, 64-query", base | (2 << 23) | (1 << 25)), ("LDS-DMA + half tiles, 128-query", base | (1 << 23)),

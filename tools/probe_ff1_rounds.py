@@ -68,8 +68,6 @@ def main():
     native.gemm([(x, w)], o10, geglu=True, tile=10)
     native.gemm([(x, w)], o9, geglu=True, tile=9)
     lib = native.load()
-    import ctypes
-    lib.mi355x_get_stat.argtypes = [ctypes.c_char_p]
     n0 = lib.mi355x_get_stat(b"g11")
     native.gemm([(x, w)], o11, geglu=True, tile=11)
     torch.cuda.synchronize()
