@@ -38,7 +38,7 @@ from .lowering import Lowering
 from .packing import PackCache, Unsupported, _expect, cname, isa, kids, launches
 from .sam import CompiledSAMViT
 
-#: class names of HQ-SAM's decoder adapters (segment_anything/hq_sam.py:16-412): that decoder branch is not lowered
+#: class names of HQ-SAM's decoder adapters (segment_anything/hq_sam.py:16-412): refused here; engine/sam_hq.py lowers a tree that has them
 HQ_NODES = ("HQSAMAdapter", "MaskDecoderTokensExtender", "MaskPredictionAdapter", "PredictionsPostProc", "HQSAMMaskPrediction")
 NOT_A_POINT = 5  # PointType.NOT_A_POINT.value
 
@@ -151,22 +151,15 @@ class SAMDecoderLowering(Lowering):
         C = dec.embedding_dim
         _expect(C == 256 and pe.shape == (4096, C), "only the 64 x 64 x 256 SAM embedding is lowered")
         _expect(T <= 64, f"{T} prompt tokens: mi355x_sam_attention takes at most 64 keys per token self-attention")
-        tokens_node, _agg, transformer, predictions = kids(dec)
-        mp, ip = kids(predictions)
+        transformer, mp, ip = self.decoder_parts(dec)
         multimask = bool(mp.multimask_output)
         k_out = 3 if multimask else 1
         first = 1 if multimask else 0
-        io = dict(
-            emb=torch.empty(1, C, 64, 64, device=self.device, dtype=self.dtype),
-            sparse=torch.empty(P * T, C, device=self.device, dtype=self.dtype),
-            mask_in=torch.empty(P, 1, 256, 256, device=self.device, dtype=self.dtype) if has_mask else None,
-            low=torch.empty(P, k_out, 256, 256, device=self.device, dtype=self.dtype),
-            iou=torch.empty(P, 16, device=self.device, dtype=self.dtype),
-        )
+        io = self.make_io(P, T, has_mask, k_out, C)
         self.iou_cols = (1, 4) if multimask else (0, 1)
         L = 4096
         with self.in_step():
-            img = self.pool.get(L, C)
+            img = self.img = self.pool.get(L, C)  # (never returned to the pool: a subclass reads the token-major image embedding again)
             native.nchw_to_nhwc(io["emb"], img)
             if has_mask:
                 dense = self.mask_encoder(menc, io["mask_in"], img, P)
@@ -189,6 +182,26 @@ class SAMDecoderLowering(Lowering):
                 dense = self._expand(dense, P)
             self.predictions(mp, ip, x, dense, P, T, first, k_out, io)
         return io
+
+    def decoder_parts(self, dec: Any) -> tuple[Any, Any, Any]:
+        """(Transformer, MaskPrediction, IOUPrediction) of a MaskDecoder that check() accepted."""
+        _tokens, _agg, transformer, predictions = kids(dec)
+        mp, ip = kids(predictions)
+        return transformer, mp, ip
+
+    def make_io(self, P: int, T: int, has_mask: bool, k_out: int, C: int) -> dict[str, Any]:
+        """The static input and output buffers of one program."""
+        return dict(
+            emb=torch.empty(1, C, 64, 64, device=self.device, dtype=self.dtype),
+            sparse=torch.empty(P * T, C, device=self.device, dtype=self.dtype),
+            mask_in=torch.empty(P, 1, 256, 256, device=self.device, dtype=self.dtype) if has_mask else None,
+            low=torch.empty(P, k_out, 256, 256, device=self.device, dtype=self.dtype),
+            iou=torch.empty(P, 16, device=self.device, dtype=self.dtype),
+        )
+
+    def mask_head(self, up1: Tensor, P: int, wct2: Tensor, bias: Tensor, hyper: Tensor, io: dict[str, Any]) -> None:
+        """ConvTranspose2d(64 -> 32) + GELU + hypernetwork contraction of the upscaled embedding [P, 128, 128, 64] -> io["low"]."""
+        native.sam_mask_head(up1, P, 128, 128, wct2, bias, hyper, io["low"])
 
     def _ln(self, x: Tensor, node: Any) -> Tensor:
         return self.layernorm(x, node)
@@ -370,7 +383,7 @@ class SAMDecoderLowering(Lowering):
         native.convt2x2_ln_gelu(y, 64, 4, self._f32(ln.weight), self._f32(ln.bias), float(ln.eps), up1, scatter_hw=(64, 64))
         self.pool.put(y)
         wct2 = self.cache.get(("sam_ct2",) + PackCache.ident(ct2.weight), lambda: ct2.weight.detach().to(self.device, torch.float32).permute(0, 2, 3, 1).reshape(64, 128).contiguous())
-        native.sam_mask_head(up1, P, 128, 128, wct2, self._f32(ct2.bias), hyper.view(P, 4, 32)[:, :k_out], io["low"])
+        self.mask_head(up1, P, wct2, self._f32(ct2.bias), hyper.view(P, 4, 32)[:, :k_out], io)
         # IoU head on token 0 (output padded to 16 columns)
         ich = kids(ip)
         _expect(len(ich) == 4 and isa(ich[2], "MultiLinear"), "unexpected IOUPrediction layout")
@@ -387,6 +400,8 @@ class CompiledSegmentAnything:
     """`fast = CompiledSegmentAnything(sam)`: `fast.predict(...)` == `sam.predict(...)` (same signature, shapes and dtypes) on the MI355X
     kernels, and `fast.predict_batch(...)` for many prompt sets against one image embedding.  An unrecognised tree (HQ-SAM's decoder
     adapters, ...) runs the stock forward with a RuntimeWarning and stats["whole_fallback"] set."""
+
+    lowering_cls = SAMDecoderLowering
 
     def __init__(self, sam: Any, use_graph: bool = True) -> None:
         native.load()
@@ -410,7 +425,7 @@ class CompiledSegmentAnything:
 
     def _fallback_reason(self) -> Optional[str]:
         try:
-            SAMDecoderLowering(torch.device("meta"), self.dtype).check(self.sam)
+            self.lowering_cls(torch.device("meta"), self.dtype).check(self.sam)
         except Unsupported as exc:
             return str(exc)
         return None
@@ -437,7 +452,7 @@ class CompiledSegmentAnything:
                 self.bad_keys.clear()
                 self.cache.sweep()
             try:
-                low = SAMDecoderLowering(self.device, self.dtype, self.cache)
+                low = self.lowering_cls(self.device, self.dtype, self.cache)
                 io = low.lower(self.sam, P, T, has_mask, self._dense_pe())
             except Unsupported as exc:
                 self.bad_keys[key] = str(exc)
@@ -457,6 +472,10 @@ class CompiledSegmentAnything:
         features = self._vit(self.sam.preprocess_image(image))
         return _embedding(self.sam)(features=features, original_image_size=(image.height, image.width))
 
+    def _tokens(self) -> Tensor:
+        """The decoder's own tokens [n, 256], the head of every prompt's token sequence."""
+        return kids(kids(self.sam.mask_decoder)[0])[1].weight
+
     def _sparse(self, coords: Tensor, types: Tensor, original_size: tuple[int, int]) -> Tensor:
         """[tokens | point embedding] of ONE prompt set (see _sparse_batch)."""
         return self._sparse_batch([(coords.reshape(-1, 2), types.reshape(-1))], original_size)[0]
@@ -471,7 +490,7 @@ class CompiledSegmentAnything:
         _expect(isa(m1, "Multiply") and isa(lin, "Linear") and isa(m2, "Multiply") and isa(cat, "Concatenate"), "unexpected CoordinateEncoder layout")
         te = next(m for m in pt.modules() if isa(m, "PointTypeEmbedding"))
         f = dict(device=self.device, dtype=torch.float32)
-        tok = kids(kids(self.sam.mask_decoder)[0])[1].weight.to(self.dtype)
+        tok = self._tokens().to(self.dtype)
         groups: dict[tuple[int, bool], list[int]] = {}
         for i, (_c, t) in enumerate(sets):
             groups.setdefault((int(t.numel()), bool(((t == 3) | (t == 4)).any())), []).append(i)
@@ -501,9 +520,17 @@ class CompiledSegmentAnything:
         io["sparse"].copy_(torch.cat(sparse, dim=0))
         if masks is not None:
             io["mask_in"].copy_(masks.reshape(io["mask_in"].shape))
+        self._fill_inputs(io)
         prog.run()
         a, b = low.iou_cols
-        return io["low"].clone(), io["iou"][:, a:b].clone()
+        return self._low_res(io), io["iou"][:, a:b].clone()
+
+    def _fill_inputs(self, io: dict[str, Any]) -> None:
+        """Further program inputs of a subclass, read at call time."""
+
+    def _low_res(self, io: dict[str, Any]) -> Tensor:
+        """The program's low-resolution masks as a tensor of the caller's."""
+        return io["low"].clone()
 
     def _postprocess(self, low: Tensor, original_size: tuple[int, int], binarize: bool) -> Tensor:
         R = self.sam.image_encoder_resolution

@@ -51,10 +51,16 @@ STRUCT_NAMES = {
 }
 _abi = abi.read(STRUCT_NAMES)
 globals().update({cls.__name__: cls for cls in _abi.structs.values()})  # GemmSeg ... VaeBlendArgs: real ctypes.Structure subclasses
+#: the same for include/mi355x_refiners_sam_hq.h, the HQ-SAM extension of the ABI (mi355x_refiners.h itself is a frozen list)
+SAM_HQ_STRUCT_NAMES = {"mi355x_sam_hq_mask_head_args": "SamHqMaskHeadArgs", "mi355x_sam_mask_head_up_args": "SamMaskHeadUpArgs"}
+_abi_sam_hq = abi.read(SAM_HQ_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_sam_hq.h")
+globals().update({cls.__name__: cls for cls in _abi_sam_hq.structs.values()})
 _K = _abi.constants
 
 #: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
 EXPORTS = list(_abi.functions)
+#: every symbol include/mi355x_refiners_sam_hq.h declares
+EXPORTS_SAM_HQ = list(_abi_sam_hq.functions)
 #: exported for probing and A/B runs, by design not in the header (no stable contract): name -> (restype, argtypes), applied by load() like the header's
 UNSTABLE = {
     "mi355x_set_option": (C.c_int, [C.c_char_p, C.c_int]),
@@ -150,7 +156,7 @@ def load(path: Optional[Path] = None) -> C.CDLL:
         lib = C.CDLL(str(p))
     except OSError as e:  # e.g. no HIP runtime on this machine
         raise NativeError(f"cannot load {p}: {e}") from e
-    for name, (restype, argtypes) in {**_abi.functions, **UNSTABLE}.items():
+    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **UNSTABLE}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.mi355x_abi_version() != ABI_VERSION:
@@ -1097,6 +1103,58 @@ def sam_postprocess_masks(low: Tensor, R: int, scaled: tuple[int, int], out: Ten
         assert out.dtype in (torch.uint8, torch.bool)
         a.binarize, a.threshold = 1, float(threshold)
     _launch("mi355x_sam_postprocess_masks", (C.byref(a),), "mi355x_sam_postprocess_masks")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ HQ-SAM mask prediction (csrc/sam_hq.hip)
+def ln2d_gelu_wide(x: Tensor, C_: int, gamma: Tensor, beta: Tensor, eps: float, out: Tensor, scatter_hw: tuple[int, int]) -> Tensor:
+    """convt2x2_ln_gelu with scatter_hw for C_ = 128 or 256: x [M, >= 4*C_] (four groups (dy, dx) of C_ columns) -> out [4*M, >= C_] NHWC rows."""
+    assert x.dim() == 2 and out.dim() == 2 and x.stride(1) == 1 and out.stride(1) == 1 and x.dtype == out.dtype
+    assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.numel() == C_ == beta.numel()
+    M = x.shape[0]
+    assert x.shape[1] >= 4 * C_ and out.shape[0] == 4 * M and out.shape[1] >= C_
+    _launch("mi355x_ln2d_gelu_wide", (dtype_code(x.dtype), x.data_ptr(), x.stride(0), M, C_, gamma.data_ptr(), beta.data_ptr(), eps, out.data_ptr(), out.stride(0),
+                                     scatter_hw[0], scatter_hw[1]), "mi355x_ln2d_gelu_wide", keep=(gamma, beta))
+    return out
+
+
+def sam_mask_head_up(x: Tensor, P: int, Hin: int, Win: int, w: Tensor, bias: Tensor, hyper: Tensor, out: Tensor, u: Tensor) -> Tensor:
+    """sam_mask_head that also stores the upscaled embedding: u [P*2Hin*2Win, >= 32] rows (columns 32.. of a wider row are left alone)."""
+    assert x.dim() == 2 and x.stride(1) == 1 and x.shape[0] == P * Hin * Win and x.shape[1] >= 64 and w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (64, 128)
+    assert bias.dtype == torch.float32 and bias.numel() == 32 and hyper.dim() == 3 and hyper.stride(2) == 1 and hyper.shape[0] == P
+    nk = hyper.shape[1]
+    assert out.dim() == 4 and tuple(out.shape[1:]) == (nk, 2 * Hin, 2 * Win) and out.stride(3) == 1 and out.stride(2) == 2 * Win and out.stride(1) == 4 * Hin * Win
+    assert u.dim() == 2 and u.stride(1) == 1 and u.shape[0] == 4 * P * Hin * Win and u.shape[1] >= 32 and u.dtype == x.dtype
+    a = SamMaskHeadUpArgs()
+    a.dtype = dtype_code(x.dtype)
+    a.P, a.Hin, a.Win, a.nk = P, Hin, Win, nk
+    a.x, a.ldx, a.w, a.bias = x.data_ptr(), x.stride(0), w.data_ptr(), bias.data_ptr()
+    a.hyper, a.ld_hyper, a.hyper_batch_stride = hyper.data_ptr(), hyper.stride(1), hyper.stride(0)
+    a.out, a.out_batch_stride = out.data_ptr(), out.stride(0)
+    a.u, a.ldu = u.data_ptr(), u.stride(0)
+    _launch("mi355x_sam_mask_head_up", (C.byref(a),), "mi355x_sam_mask_head_up", keep=(w, bias))
+    return out
+
+
+def sam_hq_mask_head(y: Tensor, P: int, H: int, W: int, gamma: Tensor, beta: Tensor, eps: float, w2: Tensor, b2: Tensor, h: Tensor, fq: Tensor, out: Tensor) -> Tensor:
+    """y [P*H*W, >= 64] rows; gamma / beta float32 [64]; w2 float32 [32, 9, 64]; b2 float32 [32]; h [P, 32] (a view, unit column stride);
+    fq [(H/2)*(W/2), >= 128] in quadrant layout; out [P, 1, H, W]."""
+    assert y.dim() == 2 and y.stride(1) == 1 and y.shape[0] == P * H * W and y.shape[1] >= 64
+    assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.numel() == 64 == beta.numel()
+    assert w2.dtype == torch.float32 and w2.is_contiguous() and tuple(w2.shape) == (32, 9, 64) and b2.dtype == torch.float32 and b2.numel() == 32
+    assert h.dim() == 2 and tuple(h.shape) == (P, 32) and h.stride(1) == 1 and h.dtype == y.dtype
+    assert fq.dim() == 2 and fq.stride(1) == 1 and fq.shape[0] == (H // 2) * (W // 2) and fq.shape[1] >= 128 and fq.dtype == y.dtype
+    assert out.dim() == 4 and tuple(out.shape) == (P, 1, H, W) and out.stride(3) == 1 and out.stride(2) == W and out.dtype == y.dtype
+    a = SamHqMaskHeadArgs()
+    a.dtype = dtype_code(y.dtype)
+    a.P, a.H, a.W = P, H, W
+    a.y, a.ldy = y.data_ptr(), y.stride(0)
+    a.gamma, a.beta, a.eps = gamma.data_ptr(), beta.data_ptr(), eps
+    a.w2, a.b2 = w2.data_ptr(), b2.data_ptr()
+    a.h, a.h_stride = h.data_ptr(), h.stride(0)
+    a.fq, a.ldf = fq.data_ptr(), fq.stride(0)
+    a.out, a.out_batch_stride = out.data_ptr(), out.stride(0)
+    _launch("mi355x_sam_hq_mask_head", (C.byref(a),), "mi355x_sam_hq_mask_head", keep=(gamma, beta, w2, b2))
     return out
 
 

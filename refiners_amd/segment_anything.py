@@ -1,9 +1,9 @@
 """SegmentAnything ViT-H (image encoder, prompt encoders, mask decoder) as a Chain tree (BASELINE.json config 5).
 
 Mirrors reference src/refiners/foundationals/segment_anything/image_encoder.py:8-368 (same class names, child order and
-parameter names, hence the same state-dict keys -- checked against tests/golden/sam_vit_h_keys.json) and the HQ-SAM encoder
-hook `SAMViTAdapter` of segment_anything/hq_sam.py:230-264.  Everything here is the unfused torch path; the MI355X engine
-(refiners_amd/engine/sam.py) lowers the same tree.
+parameter names, hence the same state-dict keys -- checked against tests/golden/sam_vit_h_keys.json) and HQ-SAM
+(segment_anything/hq_sam.py: the encoder hook `SAMViTAdapter` here, `HQSAMAdapter` and its decoder side at the end of the module).
+Everything here is the unfused torch path; the MI355X engine (refiners_amd/engine/sam.py) lowers the same tree.
 
 Shapes for ViT-H: (B, 3, 1024, 1024) -> patch conv 16x16/16 -> (B, 64, 64, 1280) channels-last tokens -> 32 layers
 (14x14 windowed attention with the grid padded 64 -> 70, global attention in layers 7, 15, 23, 31, 16 heads of 80,
@@ -795,3 +795,217 @@ class SegmentAnythingH(SegmentAnything):
     @property
     def image_encoder(self) -> SAMViTH:
         return self.ensure_find(SAMViTH)
+
+
+# ==================================================================================================================== HQ-SAM (decoder side)
+# Mirrors segment_anything/hq_sam.py:16-229, 267-412 (arXiv:2306.01567): one more output token whose 3-layer MLP gives a 32-vector h, and
+# 32-channel "HQ features" at 256 x 256 = conv(upscaled dense embedding) + upscale(image embedding) + upscale(early ViT embedding); the HQ
+# mask is h . features, returned alone or added to the base SAM mask.  refiners_amd/engine/sam_hq.py lowers it.
+def _convt(cin: int, cout: int, kw: dict) -> fl.ConvTranspose2d:
+    return fl.ConvTranspose2d(in_channels=cin, out_channels=cout, kernel_size=2, stride=2, **kw)
+
+
+class CompressViTFeat(fl.Chain):
+    """context hq_sam.early_vit_embedding [B, 64, 64, vit_dim] -> [B, 32, 256, 256]."""
+
+    def __init__(self, transformer_dim: int = 256, vit_dim: int = 1024, device: Any = None, dtype: Any = None) -> None:
+        kw = dict(device=device, dtype=dtype)
+        super().__init__(
+            fl.UseContext(context="hq_sam", key="early_vit_embedding"),
+            fl.Permute(0, 3, 1, 2),
+            _convt(vit_dim, transformer_dim, kw),
+            fl.LayerNorm2d(transformer_dim, **kw),
+            fl.GeLU(),
+            _convt(transformer_dim, transformer_dim // 8, kw),
+        )
+
+
+class EmbeddingEncoder(fl.Chain):
+    """context mask_decoder.image_embedding [B, 256, 64, 64] -> [B, 32, 256, 256]."""
+
+    def __init__(self, transformer_dim: int = 256, device: Any = None, dtype: Any = None) -> None:
+        kw = dict(device=device, dtype=dtype)
+        super().__init__(
+            fl.UseContext(context="mask_decoder", key="image_embedding"),
+            _convt(transformer_dim, transformer_dim // 4, kw),
+            fl.LayerNorm2d(transformer_dim // 4, **kw),
+            fl.GeLU(),
+            _convt(transformer_dim // 4, transformer_dim // 8, kw),
+        )
+
+
+class HQFeatures(fl.Sum):
+    def __init__(self, vit_dim: int = 1024, transformer_dim: int = 256, device: Any = None, dtype: Any = None) -> None:
+        super().__init__(EmbeddingEncoder(transformer_dim, device, dtype), CompressViTFeat(transformer_dim, vit_dim, device, dtype))
+
+
+class EmbeddingMaskfeature(fl.Chain):
+    """context mask_decoder.upscaled_dense_embedding [B, 32, 65536] -> 3x3 conv, LayerNorm2d, GELU, 3x3 conv -> [B, 32, 256, 256]."""
+
+    def __init__(self, transformer_dim: int = 256, device: Any = None, dtype: Any = None) -> None:
+        kw = dict(device=device, dtype=dtype)
+        super().__init__(
+            fl.UseContext(context="mask_decoder", key="upscaled_dense_embedding"),
+            fl.Reshape(-1, transformer_dim, transformer_dim),
+            fl.Conv2d(transformer_dim // 8, transformer_dim // 4, 3, 1, 1, **kw),
+            fl.LayerNorm2d(transformer_dim // 4, **kw),
+            fl.GeLU(),
+            fl.Conv2d(transformer_dim // 4, transformer_dim // 8, 3, 1, 1, **kw),
+        )
+
+
+class DenseEmbeddingUpscalingHQ(fl.Sum):
+    def __init__(self, vit_dim: int = 1024, transformer_dim: int = 256, device: Any = None, dtype: Any = None) -> None:
+        super().__init__(EmbeddingMaskfeature(transformer_dim, device, dtype), HQFeatures(vit_dim, transformer_dim, device, dtype))
+
+
+class HQTokenMLP(fl.Chain):
+    """The HQ token (index target_num_mask_tokens of the decoder's output tokens) -> [B, 1, embedding_dim / 8]."""
+
+    def __init__(self, embedding_dim: int, num_layers: int = 3, target_num_mask_tokens: int = 5, device: Any = None, dtype: Any = None) -> None:
+        super().__init__(
+            fl.Slicing(dim=1, start=target_num_mask_tokens, end=target_num_mask_tokens + 1),
+            fl.MultiLinear(input_dim=embedding_dim, output_dim=embedding_dim // 8, inner_dim=embedding_dim, num_layers=num_layers, device=device, dtype=dtype),
+        )
+
+
+class HQSAMMaskPrediction(fl.Matmul):
+    def __init__(self, embedding_dim: int, vit_dim: int = 1024, target_num_mask_tokens: int = 5, num_layers: int = 3, device: Any = None, dtype: Any = None) -> None:
+        super().__init__(
+            HQTokenMLP(embedding_dim, num_layers=num_layers, target_num_mask_tokens=target_num_mask_tokens, device=device, dtype=dtype),
+            fl.Chain(DenseEmbeddingUpscalingHQ(vit_dim=vit_dim, transformer_dim=256, device=device, dtype=dtype), fl.Flatten(start_dim=2)),
+        )
+
+
+class MaskPredictionAdapter(fl.Concatenate, Adapter[MaskPrediction]):
+    """[base mask | HQ mask] along dim 1."""
+
+    def __init__(self, target: MaskPrediction, vit_dim: int = 1024, target_num_mask_tokens: int = 5, device: Any = None, dtype: Any = None) -> None:
+        with self.setup_adapter(target):
+            super().__init__(
+                target,
+                fl.Chain(
+                    HQSAMMaskPrediction(embedding_dim=target.embedding_dim, vit_dim=vit_dim, target_num_mask_tokens=target_num_mask_tokens, num_layers=3,
+                                        device=device, dtype=dtype),
+                    fl.Reshape(-1, target.embedding_dim, target.embedding_dim),
+                ),
+                dim=1,
+            )
+
+    @property
+    def hq_sam_mask_prediction(self) -> HQSAMMaskPrediction:
+        return self.ensure_find(HQSAMMaskPrediction)
+
+
+class MaskDecoderTokensExtender(fl.Concatenate, Adapter[MaskDecoderTokens]):
+    """[the 5 regular tokens ; hq_token]: the new token is a weight of the adapter."""
+
+    def __init__(self, target: MaskDecoderTokens) -> None:
+        self._hq_token = [fl.Parameter(1, target.embedding_dim, device=target.device, dtype=target.dtype)]
+        with self.setup_adapter(target):
+            super().__init__(
+                target,
+                fl.Chain(fl.UseContext(context="mask_decoder", key="image_embedding"), self.hq_token),  # (the context gives the batch size)
+                dim=1,
+            )
+
+    @property
+    def regular_tokens(self) -> fl.Parameter:
+        return self.target.ensure_find(fl.Parameter)
+
+    @property
+    def hq_token(self) -> fl.Parameter:
+        return self._hq_token[0]
+
+
+class PredictionsPostProc(fl.Module):
+    """(masks [B, 2, 256, 256], iou) -> the HQ mask alone (hq_mask_only) or HQ + base, section 3.3 of the paper."""
+
+    def __init__(self, hq_mask_only: bool = False) -> None:
+        super().__init__()
+        self.hq_mask_only = hq_mask_only
+
+    def forward(self, masks_predictions: Tensor, iou_predictions: Tensor) -> tuple[Tensor, Tensor]:
+        hq = masks_predictions[:, -1:, ...]
+        if self.hq_mask_only:
+            return hq, iou_predictions
+        base = masks_predictions[:, :-1, ...]
+        assert base.shape[1] == 1
+        return hq + base, iou_predictions
+
+
+class HQSAMAdapter(fl.Chain, Adapter[SegmentAnything]):
+    """HQ-SAM on a single-mask SegmentAnything: `HQSAMAdapter(sam, weights=...).inject()`, then use `sam` as usual.  Weight keys:
+    `Chain.HQSAMMaskPrediction.*` and `MaskDecoderTokensExtender.hq_token.*`."""
+
+    def init_context(self) -> Contexts:
+        return {"hq_sam": {"early_vit_embedding": None}}
+
+    def __init__(self, target: SegmentAnything, hq_mask_only: bool = False, weights: dict[str, Tensor] | None = None) -> None:
+        # weight-key prefix -> the module that holds those weights (per adapter: the reference keeps ONE class-level dict, so that a second
+        # adapter's modules replace the first's in `weights` / `load_weights`)
+        self._adapter_modules: dict[str, fl.Module] = {}
+        self.vit_embedding_dim = target.image_encoder.embedding_dim
+        self.target_num_mask_tokens = target.mask_decoder.num_multimask_outputs + 2
+        with self.setup_adapter(target):
+            super().__init__(target)
+        if target.mask_decoder.multimask_output:
+            raise NotImplementedError("Multi-mask mode is not supported in HQSAMAdapter.")
+        dec = target.mask_decoder
+        self._mask_prediction_adapter = [MaskPredictionAdapter(dec.ensure_find(MaskPrediction), self.vit_embedding_dim, self.target_num_mask_tokens, dec.device, dec.dtype)]
+        self._adapter_modules["Chain.HQSAMMaskPrediction"] = self.mask_prediction_adapter.hq_sam_mask_prediction
+        self._image_encoder_adapter = [SAMViTAdapter(target.image_encoder)]
+        self._predictions_post_proc = [PredictionsPostProc(hq_mask_only)]
+        self._mask_decoder_tokens_extender = [MaskDecoderTokensExtender(dec.ensure_find(MaskDecoderTokens))]
+        self._adapter_modules["MaskDecoderTokensExtender.hq_token"] = self.mask_decoder_tokens_extender.hq_token
+        if weights is not None:
+            self.load_weights(weights)
+        if dec.device.type != "meta":  # (the reference moves the whole target; a model whose ViT stays on "meta" cannot be: only what was added)
+            for module in self._adapter_modules.values():
+                module.to(device=dec.device, dtype=dec.dtype)
+
+    @property
+    def weights(self) -> dict[str, Tensor]:
+        return {f"{name}.{k}": v for name, module in self._adapter_modules.items() for k, v in module.state_dict().items()}
+
+    def load_weights(self, weights: dict[str, Tensor], assign: bool = False) -> None:
+        for name, module in self._adapter_modules.items():
+            module.load_state_dict({k.removeprefix(f"{name}."): v for k, v in weights.items() if k.startswith(f"{name}.")}, **({"assign": True} if assign else {}))
+
+    @property
+    def mask_decoder_tokens_extender(self) -> MaskDecoderTokensExtender:
+        return self._mask_decoder_tokens_extender[0]
+
+    @property
+    def mask_prediction_adapter(self) -> MaskPredictionAdapter:
+        return self._mask_prediction_adapter[0]
+
+    @property
+    def image_encoder_adapter(self) -> SAMViTAdapter:
+        return self._image_encoder_adapter[0]
+
+    @property
+    def predictions_post_proc(self) -> PredictionsPostProc:
+        return self._predictions_post_proc[0]
+
+    @property
+    def hq_mask_only(self) -> bool:
+        return self.predictions_post_proc.hq_mask_only
+
+    @hq_mask_only.setter
+    def hq_mask_only(self, value: bool) -> None:
+        self.predictions_post_proc.hq_mask_only = value
+
+    def inject(self, parent: fl.Chain | None = None) -> "HQSAMAdapter":
+        self.mask_decoder_tokens_extender.inject()
+        self.mask_prediction_adapter.inject()
+        self.image_encoder_adapter.inject()
+        self.target.mask_decoder.insert_after_type(Predictions, self.predictions_post_proc)
+        return super().inject(parent)
+
+    def eject(self) -> None:
+        self.mask_decoder_tokens_extender.eject()
+        self.mask_prediction_adapter.eject()
+        self.image_encoder_adapter.eject()
+        self.target.mask_decoder.remove(self.predictions_post_proc)
+        super().eject()
