@@ -1,5 +1,6 @@
 // Layout / glue kernels of the UNet step: all HBM-bound, grid-stride, 16-byte vectorised where the layout allows.
 #include "common.cuh"
+#include "solver_update.cuh"
 #include "../../include/mi355x_refiners.h"
 
 #include <stdio.h>
@@ -115,8 +116,7 @@ __global__ __launch_bounds__(256) void cfg_ddim_kernel(T* __restrict__ x, const 
         const float u = to_f32(uo[i]), c = to_f32(uo[n + i]);
         const float eps = u + cfg * (c - u);
         const float xv = to_f32(x[i]);
-        const float x0 = (xv - s1a * eps) / sa;
-        x[i] = from_f32<T>(sap * x0 + s1ap * eps);
+        x[i] = from_f32<T>(ddim_update(xv, eps, sa, s1a, sap, s1ap));
     }
 }
 
@@ -131,8 +131,8 @@ __global__ __launch_bounds__(256) void cfg_linear_kernel(T* __restrict__ x, cons
         const float u = to_f32(uo[i]), c = to_f32(uo[n + i]);
         const float eps = u + cfg * (c - u);
         const float xv = to_f32(x[i]);
-        const float d = hx * xv + he * eps;
-        const float xn = kx * xv + ke * eps + kd * d + kp * to_f32(hist[i]);
+        float d;
+        const float xn = linear_update<T>(xv, eps, to_f32(hist[i]), hx, he, kx, ke, kd, kp, d);
         const T xs = from_f32<T>(xn);
         x[i] = xs;
         hist[i] = from_f32<T>(d);

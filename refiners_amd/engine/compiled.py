@@ -109,6 +109,7 @@ class CompiledUNet:
         self.prologue_key: Any = None
         self.prologue_refs: Any = None  # the staged source tensors themselves (see _ident)
         self.stats: dict[str, Any] = {}
+        self.lowerings, self.prologue_runs = 0, 0  # over this engine's life; shown in `stats` (a re-lowering replaces the dict, not the counts)
 
     # -- context plumbing ----------------------------------------------------------------------------------
     def _contexts(self) -> dict[str, dict[str, Any]]:
@@ -180,8 +181,10 @@ class CompiledUNet:
         self.low, self.io, self.graph, self.prologue_key, self.prologue_refs = low, io, None, None, None
         from . import tuning
 
+        self.lowerings += 1
         self.stats = dict(low.stats, step_ops=launches(low.step), prologue_ops=launches(low.prologue), pool_bytes=low.step_pool.bytes() + low.prologue_pool.bytes(),
-                          weight_prefetch=pf, gemm_tuning=tuning.summary(), ln_fuse=low.ln_fuse, qkv_merge=low.qkv_merge)
+                          weight_prefetch=pf, gemm_tuning=tuning.summary(), ln_fuse=low.ln_fuse, qkv_merge=low.qkv_merge,
+                          lowerings=self.lowerings, prologue_runs=self.prologue_runs)
 
     def _out_channels(self) -> int:
         last = [m for m in self.unet.modules() if isa(m, "Conv2d")][-1]
@@ -195,8 +198,9 @@ class CompiledUNet:
         io.timestep.copy_(ts.expand(io.timestep.shape[0]) if ts.numel() == 1 else ts)
         if io.step_rows is not None:
             io.step_rows.copy_(self.rows_table[int(got["step_index"])])
+        lcm = getattr(self.low, "lcm_scale", None)  # SDXLLcmAdapter's condition scale: a prologue input (UNetLowering._fold_condition_scale)
         pk = (_ident(got.get("timesteps_all")), _ident(got["pooled"]), _ident(got["time_ids"]), tuple(_ident(v) for v in got["tokens"].values()), tuple(_ident(v) for v in got["conditions"].values()),
-              tuple(_ident(f) for feats in got.get("t2i", {}).values() for f in feats))
+              tuple(_ident(f) for feats in got.get("t2i", {}).values() for f in feats), None if lcm is None else lcm())
         if pk == self.prologue_key:
             return False
         if io.pooled is not None:
@@ -299,6 +303,8 @@ class CompiledUNet:
     def run_prologue(self) -> None:
         assert self.low is not None
         native.replay(self.low.prologue)
+        self.prologue_runs += 1
+        self.stats["prologue_runs"] = self.prologue_runs
         self.check_handovers()  # once per prompt: a host round trip here is nothing next to the prologue's ~290 launches
 
     CHECK_EVERY = 16  # replays of the step program between two looks at the hand-over error words (one stacked .any() + one host sync)
@@ -355,11 +361,17 @@ class CompiledSDXL:
     scaling then run as ONE kernel (mi355x_cfg_linear_step) and the two cat(x, x) copies disappear from the step.
     SD1.5 UNets work too: leave `pooled_text_embedding` / `time_ids` out of `set_inputs`.
 
+    `classifier_free_guidance=False` (the reference's `sdxl.classifier_free_guidance = False`, model.py:128-159: LCM, LCM-LoRA, SDXL-Lightning):
+    the UNet runs on x alone -- embeddings of n rows, a program lowered for (n, C, H, W) -- and the update is mi355x_ddim_step /
+    mi355x_linear_step, the same arithmetic with eps = the UNet's output.  `condition_scale` and `cfg_split` are then ignored and an injected
+    SAG adapter gets no second pass (the reference evaluates it inside the CFG branch only).  It is a live attribute: assigning it drops the
+    captured graph and the priming state, as assigning `solver` does.
+
     The per-step host work is: two tiny device copies (timestep, solver coefficients) and one hipGraphLaunch.  The Chain
     tree's context store is not touched per step (the reference spends ~19 000 Python calls per step on it)."""
 
     def __init__(self, unet: Any, num_inference_steps: int = 50, condition_scale: float = 5.0, use_graph: bool = True, lora_mode: str = "fused",
-                 solver: Any = None, cfg_split: Optional[bool] = None) -> None:
+                 solver: Any = None, cfg_split: Optional[bool] = None, classifier_free_guidance: bool = True) -> None:
         from ..latent_diffusion.sampling import DDIM
 
         self.unet = unet
@@ -381,6 +393,8 @@ class CompiledSDXL:
         self.hist: Optional[Tensor] = None
         self.primed, self.primed_key = False, None
         self._condition_scale = condition_scale
+        self._cfg = bool(classifier_free_guidance)
+        self._inputs_guided: Optional[bool] = None  # the mode the staged inputs were given in (see the classifier_free_guidance setter)
         self.x: Optional[Tensor] = None
         self.graph_key: Any = None
         self.inputs: dict[str, Any] = {}
@@ -395,6 +409,17 @@ class CompiledSDXL:
         self._condition_scale = value
         self.coef_table = None
         self.graph = None  # self-attention guidance bakes sag.scale / condition_scale into the captured launches as a host scalar
+
+    @property
+    def classifier_free_guidance(self) -> bool:
+        return self._cfg
+
+    @classifier_free_guidance.setter
+    def classifier_free_guidance(self, value: bool) -> None:  # another batch (n against 2n rows), another update kernel
+        if bool(value) != self._cfg:
+            self._cfg = bool(value)
+            self.graph, self.graph_key = None, None
+            self.primed, self.primed_key = False, None
 
     @property
     def solver(self) -> Any:
@@ -426,7 +451,10 @@ class CompiledSDXL:
         if not hasattr(self.solver, "sag_coefficients") or (torch.is_tensor(ts) and ts.is_floating_point()):
             self.sag_table = None
         else:
-            self.sag_table = torch.tensor([[0.0, *self.solver.sag_coefficients(s)] for s in range(self.solver.num_inference_steps)], dtype=torch.float32, device=device)
+            try:
+                self.sag_table = torch.tensor([[0.0, *self.solver.sag_coefficients(s)] for s in range(self.solver.num_inference_steps)], dtype=torch.float32, device=device)
+            except IndexError:  # the mirror's Euler refuses for every spacing (its trailing timesteps are integers, but that combination has no golden yet)
+                self.sag_table = None
         self.sag_coef = torch.zeros(3, dtype=torch.float32, device=device)
 
     def set_inputs(self, x: Tensor, *, clip_text_embedding: Tensor, pooled_text_embedding: Optional[Tensor] = None, time_ids: Optional[Tensor] = None,
@@ -434,7 +462,16 @@ class CompiledSDXL:
                    t2i_features: Optional[dict[str, Any]] = None, generator: Optional[torch.Generator] = None) -> None:
         """x: (N, 4, H, W) initial latents; embeddings are [negative ; conditional] stacks of 2N rows;
         `conditions` maps a ControlLora name to its control image, (2N, 3, 8H, 8W) or ONE picture (1, 3, 8H, 8W) for the whole batch; `t2i_features` maps a T2I-Adapter name to
-        the tuple its `compute_condition_features` returned (batch 1 or 2N)."""
+        the tuple its `compute_condition_features` returned (batch 1 or 2N).
+        With `classifier_free_guidance=False` there is no negative half: embeddings have N rows, pictures and features 1 or N."""
+        if not self._cfg:
+            n = x.shape[0]
+            for what, t in (("clip_text_embedding", clip_text_embedding), ("pooled_text_embedding", pooled_text_embedding), ("time_ids", time_ids),
+                            ("clip_image_embedding", clip_image_embedding)):
+                assert t is None or t.shape[0] == n, f"classifier_free_guidance=False: {what} has {t.shape[0]} rows, the latents have {n} (no [negative ; conditional] stack)"
+            for what, t in [(k, v) for k, v in (conditions or {}).items()] + [(k, f) for k, feats in (t2i_features or {}).items() for f in feats]:
+                assert t.shape[0] in (1, n), f"classifier_free_guidance=False: condition '{what}' has {t.shape[0]} rows, expected 1 or {n}"
+        self._inputs_guided = self._cfg
         self.generator = generator  # stochastic solvers (LCM) draw their per-step noise from it, in the reference's order
         tokens = {("cross_attention_block", "clip_text_embedding"): clip_text_embedding}
         if clip_image_embedding is not None:
@@ -449,7 +486,7 @@ class CompiledSDXL:
             self.hist = torch.zeros_like(self.x)
             self.graph = None
         self.x.copy_(x)
-        if self.linear:
+        if self.linear or not self._cfg:
             assert self.hist is not None
             self.hist.zero_()
             self.primed = False  # the model-input buffer must be (re)filled with s_0 * x before the next step
@@ -464,7 +501,7 @@ class CompiledSDXL:
     SPLIT_MAX_IMAGES = 0
 
     def _split_wanted(self, n: int) -> bool:
-        if self._sag_adapter() is not None or self.x is None or self.x.device.type != "cuda":
+        if not self._cfg or self._sag_adapter() is not None or self.x is None or self.x.device.type != "cuda":
             return False
         return self.cfg_split if self.cfg_split is not None else n <= self.SPLIT_MAX_IMAGES
 
@@ -582,7 +619,7 @@ class CompiledSDXL:
             self.engine_c.prologue_key = None  # type: ignore[union-attr]
             return
         try:
-            self.engine.prepare_explicit((2 * n,) + tuple(self.x.shape[1:]), self.x.device, dict(self.inputs, timestep=self.ts_table[0:1], timesteps_all=self.ts_table, step_index=0))
+            self.engine.prepare_explicit(((2 * n if self._cfg else n),) + tuple(self.x.shape[1:]), self.x.device, dict(self.inputs, timestep=self.ts_table[0:1], timesteps_all=self.ts_table, step_index=0))
         except Unsupported:
             return  # a tree this lowering does not know: nothing to stage, step() takes the stock Chain forward with its warning (the fallback contract)
         self.engine.prologue_key = None  # staged, not yet run: the first step() re-stages and runs the prologue
@@ -591,11 +628,24 @@ class CompiledSDXL:
         io = io if io is not None else self.engine.io
         n = self.x.shape[0]  # type: ignore[union-attr]
         io.x[:n].copy_(self.x)  # type: ignore[union-attr]
-        io.x[n:].copy_(self.x)  # type: ignore[union-attr]
+        if self._cfg:
+            io.x[n:].copy_(self.x)  # type: ignore[union-attr]
+
+    def _update(self, io: Any) -> None:
+        """The step's last launch: (guidance +) solver update + history + the next step's model input."""
+        if self._cfg:
+            native.cfg_linear_step(self.x, io.out, self.hist, io.x, self.coef)
+        elif self.linear:
+            native.linear_step(self.x, io.out, self.hist, io.x, self.coef)
+        else:
+            native.ddim_step(self.x, io.out, io.x, self.coef)
 
     @torch.no_grad()
     def step(self, step: int) -> Tensor:
         assert self.x is not None, "call set_inputs first"
+        assert self._inputs_guided in (None, self._cfg), (
+            "classifier_free_guidance was assigned after set_inputs: call set_inputs again (embeddings of "
+            f"{'2n rows, [negative ; conditional]' if self._cfg else 'n rows'})")
         if self.coef_table is None or self.coef_table.device != self.x.device:
             self._tables(self.x.device)  # condition_scale / solver changed since the last call
         eng = self.engine
@@ -604,7 +654,8 @@ class CompiledSDXL:
         if self._split_wanted(n):
             return self._split_step(step, got, n)
         eng.io_override = None
-        shape2 = (2 * n,) + tuple(self.x.shape[1:])
+        eng.sag_capture = self._cfg  # (no guidance, no Self-Attention Guidance: the tap's column mass would be computed and never read)
+        shape2 = ((2 * n if self._cfg else n),) + tuple(self.x.shape[1:])
         try:
             changed = eng.prepare_explicit(shape2, self.x.device, got)
         except Unsupported:
@@ -615,6 +666,8 @@ class CompiledSDXL:
         io, low = eng.io, eng.low
         assert io is not None and low is not None
         self.coef.copy_(self.coef_table[step])
+        if not self._cfg:  # the UNet program on x alone, then mi355x_linear_step / mi355x_ddim_step (DDIM too keeps its model input primed: no copy per step)
+            return self._linear_step(step, io, low, eng, None, ("free", eng.key))
         sag = self._sag_adapter()
         tail = None if sag is None else self._prepare_sag(sag, got, n, io, low, step)
         # everything a captured graph holds by value or by address: both programs, and for self-attention guidance the host-side ratio
@@ -652,7 +705,7 @@ class CompiledSDXL:
         """A tree the lowering refused (CompiledUNet.prepare_explicit warned and recorded why): the step runs like the reference's
         `LatentDiffusionModel.forward` (latent_diffusion/model.py:128-159) -- contexts set on the tree, `unet(cat(x, x))` through the stock
         child loop -- and only the guidance + solver update stays on the native kernel."""
-        assert self._sag_adapter() is None, "Self-Attention Guidance on a tree that is not lowered: use refiners' own pipeline"
+        assert not self._cfg or self._sag_adapter() is None, "Self-Attention Guidance on a tree that is not lowered: use refiners' own pipeline"
         unet, x = self.unet, self.x
         assert x is not None
         unet.set_timestep(got["timestep"])
@@ -667,9 +720,12 @@ class CompiledSDXL:
         for name, feats in got.get("t2i", {}).items():
             unet.set_context("t2iadapter", {f"condition_features_{name}": tuple(f.to(x.dtype) for f in feats)})
         self.coef.copy_(self.coef_table[step])
-        xin = torch.cat((x, x))
+        xin = torch.cat((x, x)) if self._cfg else x
         if not self.linear:
-            native.cfg_ddim_step(x, unet(xin).contiguous(), self.coef)
+            if self._cfg:
+                native.cfg_ddim_step(x, unet(xin).contiguous(), self.coef)
+            else:
+                native.ddim_step(x, unet(xin).contiguous(), None, self.coef)
             return x
         assert self.hist is not None
         if getattr(self.solver, "needs_noise", None) is not None and self.solver.needs_noise(step):
@@ -677,7 +733,7 @@ class CompiledSDXL:
             self.hist.copy_(noise)
         s0 = float(self.solver.input_scale(step))
         y = unet(xin * s0 if s0 != 1.0 else xin).contiguous()
-        native.cfg_linear_step(x, y, self.hist, None, self.coef)  # (no model-input buffer: the next step scales cat(x, x) itself)
+        (native.cfg_linear_step if self._cfg else native.linear_step)(x, y, self.hist, None, self.coef)  # (no model-input buffer: the next step scales its input itself)
         return x
 
     # -- self-attention guidance (xl/model.py:164-250) ---------------------------------------------------------------------------
@@ -763,15 +819,15 @@ class CompiledSDXL:
             noise = torch.randn(tuple(self.x.shape), generator=getattr(self, "generator", None), device=sdev, dtype=sdt)
             self.hist.copy_(noise)
         if not self.primed or self.primed_key != gkey:  # first step of a trajectory, or the engine re-lowered into new buffers
-            self._fill(io)  # cat(x, x) ...
-            s0 = float(self.solver.input_scale(step))
+            self._fill(io)  # cat(x, x) (x alone without guidance) ...
+            s0 = float(self.solver.input_scale(step)) if self.linear else 1.0  # (DDIM does not scale its model input)
             if s0 != 1.0:
                 io.x.mul_(s0)  # ... through Solver.scale_model_input for THIS step; later steps get it from the kernel
             self.primed, self.primed_key = True, gkey
         if not self.use_graph:
             run()
             tail()
-            native.cfg_linear_step(self.x, io.out, self.hist, io.x, self.coef)
+            self._update(io)
             return self.x
         if self.graph is None or self.graph_key != gkey:
             run()  # warm-up outside capture; reads io.x only
@@ -781,7 +837,7 @@ class CompiledSDXL:
             with torch.cuda.graph(g):
                 run()
                 tail()
-                native.cfg_linear_step(self.x, io.out, self.hist, io.x, self.coef)
+                self._update(io)
             self.graph, self.graph_key = g, gkey
         self.graph.replay()
         return self.x

@@ -18,7 +18,9 @@ step's replays ONE captured HIP graph: per-step host work is then the descriptor
 Refused with `Unsupported` -- the call then runs the mirror's host loop over the stock forward, behind a RuntimeWarning, like CompiledUNet does for
 a tree it does not know: a UNet tree the lowering refuses, a solver that draws noise per step (LCM, DPM with an SDE variance), Self-Attention
 Guidance on the tree, a canvas batch other than 1, more active targets than mi355x_md_blend takes.  Out of scope: per-target ControlLora /
-ControlNet conditions and per-target IP-Adapter embeddings, the MultiUpscaler pipeline (the tiled VAE: engine/tiled_vae.py).  LoRAs are part of the tree and simply
+ControlNet conditions and per-target IP-Adapter embeddings, the MultiUpscaler pipeline (the tiled VAE: engine/tiled_vae.py), and targets
+without classifier-free guidance (`CompiledSDXL(classifier_free_guidance=False)` and its mi355x_ddim_step / mi355x_linear_step have no
+per-target form here: every target runs the guided pair).  LoRAs are part of the tree and simply
 work; so does an IP-Adapter with one embedding for every target (`md.clip_image_embedding = [negative ; conditional]`)."""
 from __future__ import annotations
 

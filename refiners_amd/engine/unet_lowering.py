@@ -132,8 +132,13 @@ class UNetLowering(BlockLowering):
         """RangeEncoder (range_adapter.py:25-44) of the step's timestep rows [B]; `table`: of all S timesteps x B rows (row b*S + s), `res`
         ([B, C], one row per batch row) then enters as a per-group row bias."""
         ch = kids(enc)
+        csb = None
+        if len(ch) == 6 and isa(ch[2], "ConditionScaleBlock"):  # SDXLLcmAdapter (xl/lcm.py:86-95): one constant row added to the sinusoid
+            csb, ch = ch[2], ch[:2] + ch[3:]
         _expect(len(ch) == 5 and isa(ch[0], "Lambda") and isa(ch[1], "Converter") and isa(ch[3], "SiLU"), "unexpected RangeEncoder layout")
         l1, l2 = self.linear_spec(ch[2]), self.linear_spec(ch[4])
+        if csb is not None:
+            l1 = self._fold_condition_scale(csb, l1)
         ts = self.io.timesteps if table else self.io.timestep
         R = ts.shape[0]
         sin = self.pool.get(R, enc.sinusoidal_embedding_dim)
@@ -159,6 +164,39 @@ class UNetLowering(BlockLowering):
         self.pool.put(e1)
         self.pool.put(e1s)
         return te
+
+    def _fold_condition_scale(self, block: Any, l1: LinSpec) -> LinSpec:
+        """ConditionScaleBlock = Residual(UseContext lcm.condition_scale_embedding, Converter, Linear(256 -> 320, no bias)) adds ONE constant row
+        r = W_c emb(w) to the sinusoidal embedding, and (sin + r) W1^T + b1 = sin W1^T + (r W1^T + b1): the bracket is two one-row GEMMs of the
+        PROLOGUE (the second through W1's own launch, LoRAs included), and the step's first Linear runs unchanged with that row as its bias.  emb(w)
+        is read from the adapter when the prologue runs (a prologue input: `lcm_scale` is part of the engine's prologue key), so
+        `set_condition_scale` re-runs the prologue and touches neither the lowering nor a captured step."""
+        cc = kids(block)
+        _expect(len(cc) == 3 and isa(cc[0], "UseContext") and cc[0].context == "lcm" and cc[0].key == "condition_scale_embedding" and isa(cc[1], "Converter"),
+                "unexpected ConditionScaleBlock layout")
+        lc = self.linear_spec(cc[2])
+        _expect(lc.b is None and lc.N == l1.K and not lc.geglu, "ConditionScaleBlock's Linear does not feed the RangeEncoder's first Linear")
+        adapter = block
+        while adapter is not None and not isa(adapter, "SDXLLcmAdapter"):
+            adapter = getattr(adapter, "parent", None)
+        reader = cc[0]
+
+        def embedding() -> Tensor:  # [1, 256] float32: the reference's own computation (what its context holds after every forward)
+            e = adapter.sinusoidal_embedding if adapter is not None else reader.use_context("lcm")["condition_scale_embedding"]
+            return e.reshape(1, -1)
+
+        self.lcm_scale = (lambda: float(adapter.condition_scale)) if adapter is not None else (lambda: id(reader.use_context("lcm")["condition_scale_embedding"]))
+        with self.in_prologue():
+            emb = self.pool.get(1, lc.K)
+            self.python(lambda: emb.copy_(embedding()), "lcm condition-scale embedding -> device")
+            r = self.linear(emb, lc)
+            self.pool.put(emb)
+            fb = self.pool.get(1, l1.N)
+            self.pool.pin(fb)
+            self.linear(r, l1, out=fb)
+            self.pool.put(r)
+        self.stats["lcm_condition_scale_folded"] = True
+        return LinSpec(l1.w, fb.view(-1), l1.lora, geglu=l1.geglu)
 
     def timestep_encoder(self, node: Any, ctx: UNetContext, scope: Any = None) -> None:
         """`scope`: the sub-tree whose RangeAdapter2d's read this encoder's context key (their projections are then batched)."""

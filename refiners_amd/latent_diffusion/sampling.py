@@ -128,7 +128,7 @@ class SDXLDenoiser:
         self.unet.set_time_ids(time_ids=time_ids)
 
     def __call__(self, x: Tensor, step: int, *, clip_text_embedding: Tensor, pooled_text_embedding: Tensor, time_ids: Tensor,
-                 condition_scale: float = 5.0, **kwargs: Tensor) -> Tensor:
+                 condition_scale: float = 5.0, generator: torch.Generator | None = None, **kwargs: Tensor) -> Tensor:
         if self.classifier_free_guidance:
             assert clip_text_embedding.shape[0] % 2 == 0, f"invalid batch size: {clip_text_embedding.shape[0]}"
         timestep = self.solver.timesteps[step].unsqueeze(dim=0)
@@ -145,7 +145,7 @@ class SDXLDenoiser:
                                                                      pooled_text_embedding=pooled_text_embedding, time_ids=time_ids)
         else:
             noise = self.unet(latents)
-        return self.solver(x.narrow(1, 0, 4), predicted_noise=noise, step=step)
+        return self.solver(x.narrow(1, 0, 4), predicted_noise=noise, step=step, generator=generator)  # (stochastic solvers -- LCM -- draw from it)
 
     # -- self-attention guidance (xl/model.py:164-250) -----------------------------------------------------------------------
     def _find_sag_adapter(self) -> Any:

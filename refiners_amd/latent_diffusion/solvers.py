@@ -70,12 +70,23 @@ class _Schedule:
 
 class Euler(_Schedule):
     """x' = x + eps * (sigma_next - sigma), model input x / sqrt(sigma^2 + 1); LINSPACE timesteps (float), sigmas
-    interpolated at them, a final 0 appended (euler.py:46-100)."""
+    interpolated at them, a final 0 appended (euler.py:46-100).
+
+    `timesteps_spacing="trailing"` (solver.py:229-232, integer timesteps `arange(T - 1, 0, -(T // N))`) and
+    `model_prediction_type="sample"` (euler.py:94-97: the model returns x0 and x' = r x + (1 - r) x0 with r = sigma' / sigma) are
+    what SDXL-Lightning asks of this solver; the defaults are the reference's."""
 
     def __init__(self, num_inference_steps: int, first_inference_step: int = 0, device: Any = "cpu", dtype: torch.dtype = torch.float32,
-                 num_train_timesteps: int = 1000, initial_diffusion_rate: float = 8.5e-4, final_diffusion_rate: float = 1.2e-2) -> None:
+                 num_train_timesteps: int = 1000, initial_diffusion_rate: float = 8.5e-4, final_diffusion_rate: float = 1.2e-2,
+                 timesteps_spacing: str = "linspace", model_prediction_type: str = "noise") -> None:
         super().__init__(num_inference_steps, first_inference_step, num_train_timesteps, initial_diffusion_rate, final_diffusion_rate)
-        self.timesteps = torch.tensor(np.linspace(0, num_train_timesteps - 1, num_inference_steps), dtype=torch.float32).flip(0)
+        assert timesteps_spacing in ("linspace", "trailing"), timesteps_spacing
+        assert model_prediction_type in ("noise", "sample"), model_prediction_type
+        self.timesteps_spacing, self.model_prediction_type = timesteps_spacing, model_prediction_type
+        if timesteps_spacing == "linspace":
+            self.timesteps = torch.tensor(np.linspace(0, num_train_timesteps - 1, num_inference_steps), dtype=torch.float32).flip(0)
+        else:
+            self.timesteps = torch.arange(num_train_timesteps - 1, 0, -(num_train_timesteps // num_inference_steps))
         sig = self.noise_std / self.cumulative_scale_factors
         sig = torch.tensor(np.interp(self.timesteps.numpy(), np.arange(0, len(sig)), sig.numpy()))
         self.sigmas = torch.cat([sig, torch.tensor([0.0])])
@@ -88,6 +99,7 @@ class Euler(_Schedule):
     def _noise_index(self, step: int) -> Any:
         # Euler's timesteps are FLOATS (linspace, euler.py:46-50) and the reference's add_noise / remove_noise index integer tables with them:
         # refiners itself raises here (so Self-Attention Guidance cannot be combined with Euler in the reference either)
+        # (trailing spacing has integer timesteps and the reference's indexing works there; that combination has no golden, so it is refused too)
         raise IndexError("tensors used as indices must be long, int, byte or bool tensors (Euler's float timesteps: the reference's "
                          "Solver.add_noise / remove_noise, and with them Self-Attention Guidance, do not work with this solver)")
 
@@ -103,10 +115,16 @@ class Euler(_Schedule):
     def linear_step(self, step: int) -> tuple[float, ...]:
         """(hx, he, kx, ke, kd, kp, s_next): d = eps is not needed by Euler, so hist stays unused (kd = kp = 0)."""
         s = self.sigmas.double().cpu()
+        if self.model_prediction_type == "sample":  # "eps" is the model's x0: x' = r x + (1 - r) x0
+            r = float(s[step + 1] / s[step])
+            return (0.0, 1.0, r, 1.0 - r, 0.0, 0.0, self.input_scale(step + 1))
         return (0.0, 1.0, 1.0, float(s[step + 1] - s[step]), 0.0, 0.0, self.input_scale(step + 1))
 
     def __call__(self, x: Tensor, predicted_noise: Tensor, step: int, generator: Any = None) -> Tensor:
         assert self.first_inference_step <= step < self.num_inference_steps, f"invalid step {step}"
+        if self.model_prediction_type == "sample":
+            ratio = self.sigmas[step + 1] / self.sigmas[step]
+            return ratio * x + (1 - ratio) * predicted_noise
         return x + predicted_noise * (self.sigmas[step + 1] - self.sigmas[step])
 
 

@@ -55,12 +55,16 @@ globals().update({cls.__name__: cls for cls in _abi.structs.values()})  # GemmSe
 SAM_HQ_STRUCT_NAMES = {"mi355x_sam_hq_mask_head_args": "SamHqMaskHeadArgs", "mi355x_sam_mask_head_up_args": "SamMaskHeadUpArgs"}
 _abi_sam_hq = abi.read(SAM_HQ_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_sam_hq.h")
 globals().update({cls.__name__: cls for cls in _abi_sam_hq.structs.values()})
+#: include/mi355x_refiners_solver_step.h, the guidance-free solver updates (no structs)
+_abi_solver_step = abi.read({}, abi.HEADER.parent / "mi355x_refiners_solver_step.h")
 _K = _abi.constants
 
 #: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
 EXPORTS = list(_abi.functions)
 #: every symbol include/mi355x_refiners_sam_hq.h declares
 EXPORTS_SAM_HQ = list(_abi_sam_hq.functions)
+#: every symbol include/mi355x_refiners_solver_step.h declares
+EXPORTS_SOLVER_STEP = list(_abi_solver_step.functions)
 #: exported for probing and A/B runs, by design not in the header (no stable contract): name -> (restype, argtypes), applied by load() like the header's
 UNSTABLE = {
     "mi355x_set_option": (C.c_int, [C.c_char_p, C.c_int]),
@@ -156,7 +160,7 @@ def load(path: Optional[Path] = None) -> C.CDLL:
         lib = C.CDLL(str(p))
     except OSError as e:  # e.g. no HIP runtime on this machine
         raise NativeError(f"cannot load {p}: {e}") from e
-    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **UNSTABLE}.items():
+    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **UNSTABLE}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.mi355x_abi_version() != ABI_VERSION:
@@ -977,6 +981,28 @@ def cfg_linear_step(x: Tensor, unet_out: Tensor, hist: Tensor, model_in: Optiona
     assert coef.dtype == torch.float32 and coef.numel() >= 8 and (model_in is None or (model_in.is_contiguous() and model_in.numel() == 2 * x.numel()))
     _launch("mi355x_cfg_linear_step", (dtype_code(x.dtype), x.data_ptr(), unet_out.data_ptr(), hist.data_ptr(), model_in.data_ptr() if model_in is not None else None,
                                       coef.data_ptr(), x.numel()), "mi355x_cfg_linear_step")
+    return x
+
+
+def ddim_step(x: Tensor, unet_out: Tensor, model_in: Optional[Tensor], coef: Tensor) -> Tensor:
+    """Guidance-free DDIM update, in place: x <- ddim(x, unet_out); model_in (x's shape, or None) <- the new x, the next step's model input.
+    coef: the 8-float row of cfg_ddim_step on the device (coef[0], the guidance scale, is not read) -- see mi355x_ddim_step in its header."""
+    assert x.is_contiguous() and unet_out.is_contiguous() and unet_out.numel() == x.numel() and unet_out.dtype == x.dtype
+    assert coef.dtype == torch.float32 and coef.numel() >= 5 and coef.is_cuda
+    assert model_in is None or (model_in.is_contiguous() and model_in.numel() == x.numel() and model_in.dtype == x.dtype and model_in.data_ptr() != x.data_ptr())
+    _launch("mi355x_ddim_step", (dtype_code(x.dtype), x.data_ptr(), unet_out.data_ptr(), model_in.data_ptr() if model_in is not None else None,
+                                coef.data_ptr(), x.numel()), "mi355x_ddim_step")
+    return x
+
+
+def linear_step(x: Tensor, unet_out: Tensor, hist: Tensor, model_in: Optional[Tensor], coef: Tensor) -> Tensor:
+    """Guidance-free form of cfg_linear_step: x, hist, unet_out and model_in (or None) all have x's n elements; coef: 8 float32 on the device =
+    (-, hx, he, kx, ke, kd, kp, s_next) -- see mi355x_linear_step in its header."""
+    assert x.is_contiguous() and unet_out.is_contiguous() and hist.is_contiguous() and unet_out.numel() == x.numel() == hist.numel()
+    assert unet_out.dtype == x.dtype == hist.dtype
+    assert coef.dtype == torch.float32 and coef.numel() >= 8 and (model_in is None or (model_in.is_contiguous() and model_in.numel() == x.numel() and model_in.dtype == x.dtype))
+    _launch("mi355x_linear_step", (dtype_code(x.dtype), x.data_ptr(), unet_out.data_ptr(), hist.data_ptr(), model_in.data_ptr() if model_in is not None else None,
+                                  coef.data_ptr(), x.numel()), "mi355x_linear_step")
     return x
 
 
