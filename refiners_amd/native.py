@@ -57,6 +57,10 @@ _abi_sam_hq = abi.read(SAM_HQ_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners
 globals().update({cls.__name__: cls for cls in _abi_sam_hq.structs.values()})
 #: include/mi355x_refiners_solver_step.h, the guidance-free solver updates (no structs)
 _abi_solver_step = abi.read({}, abi.HEADER.parent / "mi355x_refiners_solver_step.h")
+#: include/mi355x_refiners_swin.h, the Swin Transformer's window attention
+SWIN_STRUCT_NAMES = {"mi355x_window_attention_args": "WindowAttentionArgs"}
+_abi_swin = abi.read(SWIN_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_swin.h")
+globals().update({cls.__name__: cls for cls in _abi_swin.structs.values()})
 _K = _abi.constants
 
 #: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
@@ -65,6 +69,8 @@ EXPORTS = list(_abi.functions)
 EXPORTS_SAM_HQ = list(_abi_sam_hq.functions)
 #: every symbol include/mi355x_refiners_solver_step.h declares
 EXPORTS_SOLVER_STEP = list(_abi_solver_step.functions)
+#: every symbol include/mi355x_refiners_swin.h declares
+EXPORTS_SWIN = list(_abi_swin.functions)
 #: exported for probing and A/B runs, by design not in the header (no stable contract): name -> (restype, argtypes), applied by load() like the header's
 UNSTABLE = {
     "mi355x_set_option": (C.c_int, [C.c_char_p, C.c_int]),
@@ -160,7 +166,7 @@ def load(path: Optional[Path] = None) -> C.CDLL:
         lib = C.CDLL(str(p))
     except OSError as e:  # e.g. no HIP runtime on this machine
         raise NativeError(f"cannot load {p}: {e}") from e
-    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **UNSTABLE}.items():
+    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **UNSTABLE}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.mi355x_abi_version() != ABI_VERSION:
@@ -1129,6 +1135,28 @@ def sam_postprocess_masks(low: Tensor, R: int, scaled: tuple[int, int], out: Ten
         assert out.dtype in (torch.uint8, torch.bool)
         a.binarize, a.threshold = 1, float(threshold)
     _launch("mi355x_sam_postprocess_masks", (C.byref(a),), "mi355x_sam_postprocess_masks")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ Swin window attention (csrc/window_attention.hip)
+def window_attention(q: Tensor, k: Tensor, v: Tensor, table: Tensor, out: Tensor, num_heads: int, window_size: int, nw: int = 0, shift: int = 0,
+                     scale: Optional[float] = None) -> Tensor:
+    """q, k, v: [nW, N, H * 32] views (N = window_size^2, unit channel stride; normally three column views of the packed QKV rows);
+    table: float32 [(2 ws - 1)^2, H], the tree's own parameter; out: [nW, N, H * 32] view.  shift > 0: the windows tile grids of nw x nw
+    windows rolled by -shift and the -100 shift mask is added (see the header)."""
+    a = WindowAttentionArgs()
+    nW, N, HD = q.shape
+    assert HD == num_heads * 32 and N == window_size * window_size and tuple(k.shape) == tuple(q.shape) == tuple(v.shape) == tuple(out.shape)
+    assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1 and out.stride(2) == 1 and k.dtype == q.dtype == v.dtype == out.dtype
+    assert table.dtype == torch.float32 and table.is_contiguous() and tuple(table.shape) == ((2 * window_size - 1) ** 2, num_heads)
+    a.dtype = dtype_code(q.dtype)
+    a.nW, a.H, a.ws, a.nw, a.shift = nW, num_heads, window_size, nw, shift
+    a.q, a.ldq, a.q_win_stride = q.data_ptr(), q.stride(1), q.stride(0)
+    a.k, a.ldk, a.k_win_stride = k.data_ptr(), k.stride(1), k.stride(0)
+    a.v, a.ldv, a.v_win_stride = v.data_ptr(), v.stride(1), v.stride(0)
+    a.table, a.scale = table.data_ptr(), scale if scale is not None else 32 ** -0.5
+    a.out, a.ldo, a.o_win_stride = out.data_ptr(), out.stride(1), out.stride(0)
+    _launch("mi355x_window_attention", (C.byref(a),), "mi355x_window_attention", keep=(table,))
     return out
 
 
