@@ -352,6 +352,7 @@ int dispatch_general(const GAttnP& p, hipStream_t st) {
     TRY(2, 4)    // head dim 64 with causal masking (CLIP)
     TRY(3, 5)    // head dim 80 (SD1.5 at 640 channels)
     TRY(4, 5)    // SAM windowed: 80 + 14 + 14 bias columns, V 80
+    TRY(4, 8)    // head dim 128 (MVANet's single-head attentions)
     TRY(5, 10)   // head dim 160 (SD1.5 at 1280 channels)
     TRY(7, 5)    // SAM global: 80 + 64 + 64 bias columns, V 80
 #undef TRY

@@ -465,10 +465,10 @@ class Lowering:
         return out_t
 
     def conv(self, a: Act, spec: ConvSpec, *, rowbias: Optional[Tensor] = None, res: Optional[Tensor] = None, ups: int = 1,
-             shortcut: Optional[tuple[Act, ConvSpec]] = None, bias: Optional[Tensor] = "spec") -> Act:  # type: ignore[assignment]
+             shortcut: Optional[tuple[Act, ConvSpec]] = None, bias: Optional[Tensor] = "spec", gelu: bool = False) -> Act:  # type: ignore[assignment]
         """Implicit-GEMM convolution of a token-major image; optional fused extras:
         rowbias = per-sample channel bias (time embedding), res = residual rows, ups = nearest upsampling of the input,
-        shortcut = a second (1x1) convolution of another image accumulated into the same output tile."""
+        shortcut = a second (1x1) convolution of another image accumulated into the same output tile, gelu = the erf-GELU epilogue."""
         H, W = a.H * ups, a.W * ups
         OH, OW = (H + spec.stride - 1) // spec.stride, (W + spec.stride - 1) // spec.stride
         out = self.pool.get(a.B * OH * OW, spec.cout)
@@ -501,14 +501,14 @@ class Lowering:
         tiles128 = ((M_out + 127) // 128) * ((spec.cout + 127) // 128)
         total_kb = sum(sg[1].shape[1] for sg in segs) * self.es // 128
         tile, ksplit, ws = 0, 1, None
-        if tiles128 <= 192 and total_kb >= 96:
+        if tiles128 <= 192 and total_kb >= 96 and not gelu:
             tile, ksplit = 1, 3
             ws = self.splitk_workspace(ksplit * M_out * spec.cout)
         if lo is not None:
             sy = self.lora_sync(1, M_out, spec.lora.R)
         cs = self.colstats_for(M_out, spec.cout, OH * OW)  # most convolution outputs of a UNet are normalised next (ResidualBlock, unet.py:6-51)
         native.conv_gemm(segs, out, a.B, OH, OW, bias=b, rowbias=rowbias, rows_per_group=OH * OW, res=res, tile=tile, ksplit=ksplit, ws=ws, lora=lo, lora_sync=sy,
-                         colstats_out=cs, table_may_replace_split=True)
+                         colstats_out=cs, table_may_replace_split=True, gelu=gelu)
         if sy is not None:
             self.pool.put(sy[0])
         self.pool.put(t)

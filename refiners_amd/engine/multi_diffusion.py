@@ -148,6 +148,7 @@ class CompiledMultiDiffusion:
         self.blend_order: list[tuple[int, int, int]] = []  # (target position, chunk, row) in list order
         self.hist_of: dict[int, tuple[Any, Tensor]] = {}  # id(target) -> (target, its row of a chunk's history buffer)
         self.masks: dict[int, tuple[Any, Any, Tensor]] = {}  # id(target) -> (its opacity mask, the mask's identity, float32 device copy)
+        self.key_targets: tuple = ()  # the targets whose id() the current plan key holds
         self.ts_tables: dict[tuple, Tensor] = {}
         self.solver_cache: dict = {}
         self.graph: Optional[torch.cuda.CUDAGraph] = None
@@ -342,6 +343,7 @@ class CompiledMultiDiffusion:
         key = graph_key(chunks, targets)
         if key != self.plan_key:
             self._build_states(chunks, targets, key)
+            self.key_targets = tuple(targets)  # the key holds their id(): while it is kept they stay alive, so that no new target can be mistaken for one of them
         engine_keys = []
         for k, st in enumerate(self.states):
             self._embeddings(st, targets)

@@ -84,8 +84,10 @@ def shift_mask_model(nw: int, ws: int, shift: int) -> Tensor:
 
 
 class SwinLowering(Lowering):
-    def lower(self, swin: Any, image: Tensor, outs: list[Tensor]) -> None:
-        """image [B, 3, S, S] (static) -> outs, the static NCHW maps in the order the forward returns them (stage_n, ..., stage_1, patch_embedding)."""
+    def lower(self, swin: Any, image: Tensor, outs: list[Tensor], as_tokens: bool = False) -> None:
+        """image [B, 3, S, S] (static) -> outs, the static NCHW maps in the order the forward returns them (stage_n, ..., stage_1, patch_embedding).
+        as_tokens (MVANet's decoder reads the maps channels-last): outs are the [B * g * g, C] token rows of the same maps, no nhwc_to_nchw."""
+        self.as_tokens = as_tokens
         ch = kids(swin)
         _expect(len(ch) >= 3 and isa(ch[0], "PatchEmbedding") and isa(ch[1], "Passthrough") and all(isa(c, "Chain") for c in ch[2:]), "unexpected SwinTransformer layout")
         stages = ch[2:]
@@ -145,6 +147,13 @@ class SwinLowering(Lowering):
 
     def emit_output(self, tok: Tensor, ln: Any, B: int, g: int, out: Tensor) -> None:
         C = tok.shape[1]
+        if getattr(self, "as_tokens", False):
+            _expect(tuple(out.shape) == (B * g * g, C) and out.is_contiguous(), "output rows of another shape")
+            if ln is None:
+                native.axpby(tok, 1.0, tok, 0.0, out)  # (a copy: the blocks go on updating tok in place)
+            else:
+                native.layernorm(tok, self._w(ln.weight), self._w(ln.bias), ln.eps, out)
+            return
         _expect(tuple(out.shape) == (B, C, g, g), "output map of another shape")
         y = tok if ln is None else self.layernorm(tok, ln)
         native.nhwc_to_nchw(y.view(B, g * g, C), out, C)

@@ -61,6 +61,10 @@ _abi_solver_step = abi.read({}, abi.HEADER.parent / "mi355x_refiners_solver_step
 SWIN_STRUCT_NAMES = {"mi355x_window_attention_args": "WindowAttentionArgs"}
 _abi_swin = abi.read(SWIN_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_swin.h")
 globals().update({cls.__name__: cls for cls in _abi_swin.structs.values()})
+#: include/mi355x_refiners_mvanet.h, the streaming passes of MVANet's multi-view decoder
+MVANET_STRUCT_NAMES = {"mi355x_mvanet_pool_args": "MvanetPoolArgs", "mi355x_mvanet_gate_args": "MvanetGateArgs", "mi355x_mvanet_resize_add_args": "MvanetResizeAddArgs"}
+_abi_mvanet = abi.read(MVANET_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_mvanet.h")
+globals().update({cls.__name__: cls for cls in _abi_mvanet.structs.values()})
 _K = _abi.constants
 
 #: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
@@ -71,6 +75,8 @@ EXPORTS_SAM_HQ = list(_abi_sam_hq.functions)
 EXPORTS_SOLVER_STEP = list(_abi_solver_step.functions)
 #: every symbol include/mi355x_refiners_swin.h declares
 EXPORTS_SWIN = list(_abi_swin.functions)
+#: every symbol include/mi355x_refiners_mvanet.h declares
+EXPORTS_MVANET = list(_abi_mvanet.functions)
 #: exported for probing and A/B runs, by design not in the header (no stable contract): name -> (restype, argtypes), applied by load() like the header's
 UNSTABLE = {
     "mi355x_set_option": (C.c_int, [C.c_char_p, C.c_int]),
@@ -166,7 +172,7 @@ def load(path: Optional[Path] = None) -> C.CDLL:
         lib = C.CDLL(str(p))
     except OSError as e:  # e.g. no HIP runtime on this machine
         raise NativeError(f"cannot load {p}: {e}") from e
-    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **UNSTABLE}.items():
+    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **_abi_mvanet.functions, **UNSTABLE}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.mi355x_abi_version() != ABI_VERSION:
@@ -585,8 +591,9 @@ def conv_gemm(
     lora_sync: Optional[tuple] = None,
     colstats_out: Optional[Tensor] = None,
     table_may_replace_split: bool = False,
+    gelu: bool = False,
 ) -> Tensor:
-    """Implicit-GEMM convolution over NHWC images.
+    """Implicit-GEMM convolution over NHWC images.  gelu: the erf-GELU epilogue (geglu = 2), not combinable with ksplit.
 
     segs: (image [B,H,W,C] NHWC-contiguous or channel-sliced view, packed weight [N, ksize*ksize*C], ksize, stride, ups).
     out: [B*OH*OW, N] rows (i.e. NHWC output).
@@ -612,7 +619,8 @@ def conv_gemm(
         sg.ksize, sg.stride, sg.ups, sg.H, sg.W, sg.asym = ksize, stride, ups, h, wd, asym
         sg.kblocked = 1 if isinstance(w, KBlocked) else 0
     a.zeros = zero_page(img0.device).data_ptr()
-    _fill_epilogue(a, out, bias, rowbias, rows_per_group, res, False)
+    assert not (gelu and ksplit > 1)
+    _fill_epilogue(a, out, bias, rowbias, rows_per_group, res, 2 if gelu else False)
     keep: list = []
     if lora is not None:
         _lora_fill(a, lora, False, img0.dtype, tuple(w0.shape)[1], keep, lora_sync)
@@ -1157,6 +1165,77 @@ def window_attention(q: Tensor, k: Tensor, v: Tensor, table: Tensor, out: Tensor
     a.table, a.scale = table.data_ptr(), scale if scale is not None else 32 ** -0.5
     a.out, a.ldo, a.o_win_stride = out.data_ptr(), out.stride(1), out.stride(0)
     _launch("mi355x_window_attention", (C.byref(a),), "mi355x_window_attention", keep=(table,))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ MVANet's decoder (csrc/mvanet.hip)
+MVANET_MAX_RATIOS = _abi_mvanet.constants["MI355X_MVANET_MAX_RATIOS"]
+
+
+def mvanet_pool_rows(G: int, ratios: Sequence[int]) -> int:
+    """Rows MultiPool writes for a G x G map."""
+    return sum((G // r) ** 2 for r in ratios)
+
+
+def mvanet_pool(src: Tensor, S: int, ratios: Sequence[int], out: Tensor, split: bool) -> Tensor:
+    """MultiPool as token rows.  split=False: src [4 S S, E] = four views, pooled as their PatchMerge (side 2 S), out [rows, E].  split=True:
+    src [S S, E] = one view, out [4, rows, E]: group q pools quadrant q (PatchSplit).  Rows past the pooled ones are written as zeros."""
+    a = MvanetPoolArgs()
+    assert src.dim() == 2 and src.stride(1) == 1 and out.stride(-1) == 1 and out.shape[-1] == src.shape[1] and out.dtype == src.dtype
+    assert src.shape[0] == (1 if split else 4) * S * S and out.dim() == (3 if split else 2) and (not split or out.shape[0] == 4) and len(ratios) <= MVANET_MAX_RATIOS
+    a.dtype, a.mode, a.S, a.E, a.n_ratios = dtype_code(src.dtype), int(split), S, src.shape[1], len(ratios)
+    for i, r in enumerate(ratios):
+        a.ratio[i] = r
+    a.src, a.lds, a.out, a.ldo, a.rows = src.data_ptr(), src.stride(0), out.data_ptr(), out.stride(-2), out.shape[-2]
+    a.group_stride = out.stride(0) if split else 0
+    _launch("mi355x_mvanet_pool", (C.byref(a),), "mi355x_mvanet_pool")
+    return out
+
+
+def mvanet_gate(local: Tensor, glb: Tensor, w: Tensor, b: Tensor, out: Tensor, S: int) -> Tensor:
+    """out = local * sigmoid(w . glb + b), the gate map upsampled 2x (nearest) and split into quadrants.  local, out: [4 S S, E] (out may be
+    local); glb: [S S, E]; w [E], b [1]: the activations' dtype, read at every launch."""
+    a = MvanetGateArgs()
+    E = local.shape[1]
+    assert tuple(local.shape) == tuple(out.shape) == (4 * S * S, E) and tuple(glb.shape) == (S * S, E) and local.stride(1) == glb.stride(1) == out.stride(1) == 1
+    assert w.dtype == b.dtype == glb.dtype == out.dtype == local.dtype and w.is_contiguous() and w.numel() == E and b.numel() == 1
+    a.dtype, a.S, a.E = dtype_code(local.dtype), S, E
+    a.local, a.ldl, a.glb, a.ldg, a.w, a.b, a.out, a.ldo = local.data_ptr(), local.stride(0), glb.data_ptr(), glb.stride(0), w.data_ptr(), b.data_ptr(), out.data_ptr(), out.stride(0)
+    _launch("mi355x_mvanet_gate", (C.byref(a),), "mi355x_mvanet_gate", keep=(w, b))
+    return out
+
+
+def mvanet_resize_add(x: Tensor, x_hw: tuple[int, int], y: Tensor, out: Tensor, out_hw: tuple[int, int], B: int = 1, mode: str = "bilinear",
+                      slope_x: Optional[Tensor] = None, slope_y: Optional[Tensor] = None, x_merge: bool = False, y_merge: bool = False) -> Tensor:
+    """out = resize(f(x)) + g(y): x [B Hx Wx, E] resized to out_hw (torch's bilinear with align_corners=False, or nearest), y, out [B Ho Wo, E]; f / g =
+    PReLU with the one-element device tensor slope_x / slope_y, identity when None.  *_merge: the operand is four views read as their PatchMerge.
+    out may be y."""
+    a = MvanetResizeAddArgs()
+    E = out.shape[1]
+    (Ha, Wa), (Ho, Wo) = x_hw, out_hw
+    assert tuple(x.shape) == (B * Ha * Wa, E) and tuple(y.shape) == tuple(out.shape) == (B * Ho * Wo, E) and x.stride(1) == y.stride(1) == out.stride(1) == 1
+    assert x.dtype == y.dtype == out.dtype and all(s is None or (s.dtype == out.dtype and s.numel() == 1) for s in (slope_x, slope_y)) and mode in ("bilinear", "nearest")
+    a.dtype, a.mode, a.B, a.E = dtype_code(out.dtype), int(mode == "nearest"), B, E
+    a.Ha, a.Wa, a.Ho, a.Wo, a.a_merge, a.b_merge = Ha, Wa, Ho, Wo, int(x_merge), int(y_merge)
+    a.a, a.lda, a.b, a.ldb, a.out, a.ldo = x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), out.data_ptr(), out.stride(0)
+    a.slope_a = slope_x.data_ptr() if slope_x is not None else None
+    a.slope_b = slope_y.data_ptr() if slope_y is not None else None
+    _launch("mi355x_mvanet_resize_add", (C.byref(a),), "mi355x_mvanet_resize_add", keep=(slope_x, slope_y))
+    return out
+
+
+def mvanet_prelu(x: Tensor, slope: Tensor) -> Tensor:
+    """In-place PReLU of a contiguous tensor with the one-element device tensor `slope` (read at every launch)."""
+    assert x.is_contiguous() and slope.dtype == x.dtype and slope.numel() == 1
+    _launch("mi355x_mvanet_prelu", (dtype_code(x.dtype), x.data_ptr(), slope.data_ptr(), x.numel()), "mi355x_mvanet_prelu", keep=(slope,))
+    return x
+
+
+def mvanet_split_views(image: Tensor, out: Tensor) -> Tensor:
+    """SplitMultiView: image [1, C, H, W] -> out [5, C, H / 2, W / 2], the four quadrants and the 2 x 2 block means (bilinear 0.5x)."""
+    _one, Cc, H, W = image.shape
+    assert _one == 1 and image.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (5, Cc, H // 2, W // 2) and out.dtype == image.dtype
+    _launch("mi355x_mvanet_split_views", (dtype_code(image.dtype), image.data_ptr(), out.data_ptr(), Cc, H, W), "mi355x_mvanet_split_views")
     return out
 
 
