@@ -65,6 +65,10 @@ globals().update({cls.__name__: cls for cls in _abi_swin.structs.values()})
 MVANET_STRUCT_NAMES = {"mi355x_mvanet_pool_args": "MvanetPoolArgs", "mi355x_mvanet_gate_args": "MvanetGateArgs", "mi355x_mvanet_resize_add_args": "MvanetResizeAddArgs"}
 _abi_mvanet = abi.read(MVANET_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_mvanet.h")
 globals().update({cls.__name__: cls for cls in _abi_mvanet.structs.values()})
+#: include/mi355x_refiners_dinov2.h, the streaming passes of the DINOv2 encoder
+DINOV2_STRUCT_NAMES = {"mi355x_dinov2_pos_resample_args": "Dinov2PosResampleArgs", "mi355x_dinov2_tokens_args": "Dinov2TokensArgs"}
+_abi_dinov2 = abi.read(DINOV2_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_dinov2.h")
+globals().update({cls.__name__: cls for cls in _abi_dinov2.structs.values()})
 _K = _abi.constants
 
 #: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
@@ -77,6 +81,8 @@ EXPORTS_SOLVER_STEP = list(_abi_solver_step.functions)
 EXPORTS_SWIN = list(_abi_swin.functions)
 #: every symbol include/mi355x_refiners_mvanet.h declares
 EXPORTS_MVANET = list(_abi_mvanet.functions)
+#: every symbol include/mi355x_refiners_dinov2.h declares
+EXPORTS_DINOV2 = list(_abi_dinov2.functions)
 #: exported for probing and A/B runs, by design not in the header (no stable contract): name -> (restype, argtypes), applied by load() like the header's
 UNSTABLE = {
     "mi355x_set_option": (C.c_int, [C.c_char_p, C.c_int]),
@@ -172,7 +178,7 @@ def load(path: Optional[Path] = None) -> C.CDLL:
         lib = C.CDLL(str(p))
     except OSError as e:  # e.g. no HIP runtime on this machine
         raise NativeError(f"cannot load {p}: {e}") from e
-    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **_abi_mvanet.functions, **UNSTABLE}.items():
+    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **_abi_mvanet.functions, **_abi_dinov2.functions, **UNSTABLE}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.mi355x_abi_version() != ABI_VERSION:
@@ -1236,6 +1242,65 @@ def mvanet_split_views(image: Tensor, out: Tensor) -> Tensor:
     _one, Cc, H, W = image.shape
     assert _one == 1 and image.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (5, Cc, H // 2, W // 2) and out.dtype == image.dtype
     _launch("mi355x_mvanet_split_views", (dtype_code(image.dtype), image.data_ptr(), out.data_ptr(), Cc, H, W), "mi355x_mvanet_split_views")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ DINOv2's encoder (csrc/dinov2.hip)
+class Dinov2Axis:
+    """The tap table of one axis of mi355x_dinov2_pos_resample: per output index the first source index, the tap count and the offset of its
+    first weight in `weight` (int32 [n_out] each, float32 [len]).  Built and CHECKED on the host (the kernel reads the device copy and the
+    entry point cannot see it), then copied to `device`."""
+
+    def __init__(self, first: Tensor, count: Tensor, offset: Tensor, weight: Tensor, n_src: int, device: Any = "cpu") -> None:
+        first, count, offset = (t.to(torch.int32).contiguous() for t in (first, count, offset))
+        weight = weight.to(torch.float32).contiguous()
+        assert first.dim() == count.dim() == offset.dim() == weight.dim() == 1 and first.numel() == count.numel() == offset.numel() >= 1 and weight.numel() >= 1
+        assert bool((count >= 1).all()) and bool((first >= 0).all()) and bool((first + count <= n_src).all()), "taps outside the source axis"
+        assert bool((offset >= 0).all()) and bool((offset + count <= weight.numel()).all()), "taps outside the weight list"
+        self.n_src, self.n_out = n_src, first.numel()
+        self.host = (first, count, offset, weight)
+        self.dev = tuple(t.to(device) for t in self.host)
+
+
+def dinov2_pos_resample(src: Tensor, ty: Dinov2Axis, tx: Dinov2Axis, out: Tensor) -> Tensor:
+    """out [h * w, D] float32 = the separable filter (ty, tx) over src [Hs * Ws, D] (rows of the learned position grid, channels-last)."""
+    a = Dinov2PosResampleArgs()
+    D = src.shape[1]
+    assert src.dim() == 2 and out.dim() == 2 and src.stride(1) == 1 and out.stride(1) == 1 and out.dtype == torch.float32
+    assert tuple(src.shape) == (ty.n_src * tx.n_src, D) and tuple(out.shape) == (ty.n_out * tx.n_out, D)
+    assert all(t.device == src.device for t in ty.dev + tx.dev), "tap tables on another device"
+    a.dtype, a.Hs, a.Ws, a.h, a.w, a.D = dtype_code(src.dtype), ty.n_src, tx.n_src, ty.n_out, tx.n_out, D
+    a.src, a.lds, a.out, a.ldo = src.data_ptr(), src.stride(0), out.data_ptr(), out.stride(0)
+    a.y0, a.ny, a.wy_off, a.wy = (t.data_ptr() for t in ty.dev)
+    a.x0, a.nx, a.wx_off, a.wx = (t.data_ptr() for t in tx.dev)
+    a.wy_len, a.wx_len = ty.dev[3].numel(), tx.dev[3].numel()
+    _launch("mi355x_dinov2_pos_resample", (C.byref(a),), "mi355x_dinov2_pos_resample", keep=(src, ty, tx, out))
+    return out
+
+
+def dinov2_tokens(patch: Tensor, pos: Tensor, cls: Tensor, pos0: Tensor, reg: Optional[Tensor], out: Tensor, B: int, rows: Optional[int] = None) -> Tensor:
+    """out [B * rows, D]: per image the class row (cls + pos0), the register rows (reg [R, D] or None), the n patch rows + pos [n, D] (float32),
+    then zero rows up to `rows` (default 1 + R + n).  patch [B * n, D]."""
+    a = Dinov2TokensArgs()
+    D = patch.shape[1]
+    n, R = pos.shape[0], 0 if reg is None else reg.shape[0]
+    rows = rows if rows is not None else 1 + R + n
+    assert patch.dim() == 2 and patch.shape[0] == B * n and tuple(pos.shape) == (n, D) and pos.dtype == torch.float32 and tuple(out.shape) == (B * rows, D) and rows >= 1 + R + n
+    assert patch.stride(1) == pos.stride(1) == out.stride(1) == 1 and cls.numel() == pos0.numel() == D and cls.is_contiguous() and pos0.is_contiguous()
+    assert patch.dtype == cls.dtype == pos0.dtype == out.dtype and (reg is None or (reg.dtype == out.dtype and reg.shape[1] == D and reg.stride(1) == 1))
+    a.dtype, a.B, a.n, a.R, a.D, a.rows = dtype_code(out.dtype), B, n, R, D, rows
+    a.patch, a.ldp, a.pos, a.ldpos, a.cls, a.pos0 = patch.data_ptr(), patch.stride(0), pos.data_ptr(), pos.stride(0), cls.data_ptr(), pos0.data_ptr()
+    a.reg, a.ldr = (reg.data_ptr(), reg.stride(0)) if reg is not None else (None, 0)
+    a.out, a.ldo = out.data_ptr(), out.stride(0)
+    _launch("mi355x_dinov2_tokens", (C.byref(a),), "mi355x_dinov2_tokens", keep=(pos, cls, pos0, reg))
+    return out
+
+
+def glu_silu(x: Tensor, out: Tensor) -> Tensor:
+    """out [M, F] = x[:, :F] * silu(x[:, F:]) for x [M, 2 F]: the reference's GLU(SiLU())."""
+    M, F2 = x.shape
+    assert x.dim() == 2 and F2 % 2 == 0 and tuple(out.shape) == (M, F2 // 2) and x.stride(1) == out.stride(1) == 1 and x.dtype == out.dtype
+    _launch("mi355x_glu_silu", (dtype_code(x.dtype), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), M, F2 // 2), "mi355x_glu_silu")
     return out
 
 
