@@ -69,7 +69,8 @@ int mi355x_device_info(char* buf, int32_t buflen);
  * Long-K / small-MN problems (the 32x32-resolution convolutions: 320 tiles, K = 11520) can be split along K (`ksplit`).
  * Epilogue order: + bias[n] ; + rowbias[(m / rows_per_group)*ld_rowbias + n] ; geglu: v = a * gelu_erf(g) ;
  * (or v = gelu_erf(v) when geglu == 2, v = v * sigmoid(1.702 v) when geglu == 3: fl.GeLU with approximation NONE / SIGMOID,
- * src/refiners/fluxion/layers/activations.py:83-125; v = max(v, 0) when geglu == 4: fl.ReLU) ;
+ * src/refiners/fluxion/layers/activations.py:83-125; v = max(v, 0) when geglu == 4: fl.ReLU; v = max(v, 0)^2 when geglu == 5: ELLA's
+ * SquaredReLU, foundationals/latent_diffusion/ella_adapter.py) ;
  * + res[m*ldres + n] ; convert to dtype ; store out[m*ldo + n].
  */
 #define MI355X_MAX_SEG 3
@@ -106,8 +107,9 @@ typedef struct {
     const void* rowbias;    /* [M / rows_per_group][ld_rowbias] or NULL (RangeAdapter2d time-embedding bias) */
     int64_t ld_rowbias;
     int32_t rows_per_group;
-    int32_t geglu;          /* epilogue activation: 0 none, 1 GEGLU (value * gelu_erf(gate), packed rows), 2 gelu_erf, 3 quick-GELU, 4 ReLU on every column
-                               (4 is newer than the other codes within ABI 7: a library built before it applies NO activation for 4, so the
+    int32_t geglu;          /* epilogue activation: 0 none, 1 GEGLU (value * gelu_erf(gate), packed rows), 2 gelu_erf, 3 quick-GELU, 4 ReLU, 5 squared ReLU
+                               (max(v, 0)^2) on every column
+                               (4 and 5 are newer than the other codes within ABI 7: a library built before them applies NO activation for them, so the
                                package must run on the library built from its own tree, which build() and build_native guarantee) */
     const void* res;        /* [M][ldres] or NULL */
     int64_t ldres;

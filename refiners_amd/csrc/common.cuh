@@ -119,8 +119,13 @@ MI_DEV float erf_as(float x) {
 MI_DEV float gelu_exact(float x) { return 0.5f * x * (1.0f + erf_as(x * 0.70710678118654752440f)); }
 // CLIP's "quick GELU" (GeLUApproximation.SIGMOID, fluxion/layers/activations.py:83-118)
 MI_DEV float quick_gelu(float x) { return x / (1.0f + __expf(-1.702f * x)); }
-// the GEMM epilogue's per-column activation (gemm_params.cuh `gelu`): 1 erf-GELU, 2 quick GELU, 3 ReLU
-MI_DEV float epi_act(int kind, float x) { return kind == 1 ? gelu_exact(x) : (kind == 2 ? quick_gelu(x) : fmaxf(x, 0.0f)); }
+// the GEMM epilogue's per-column activation (gemm_params.cuh `gelu`): 1 erf-GELU, 2 quick GELU, 3 ReLU, 4 squared ReLU
+MI_DEV float epi_act(int kind, float x) {
+    if (kind == 1) return gelu_exact(x);
+    if (kind == 2) return quick_gelu(x);
+    const float r = fmaxf(x, 0.0f);
+    return kind == 4 ? r * r : r;
+}
 // x * sigmoid(x) with ONE v_rcp_f32 (1 ulp) instead of the IEEE division's ten instructions: the GroupNorm apply pass is 8 SiLUs per 16 bytes, and at the
 // step's sizes (Infinity-Cache resident tensors) the division was a sixth of it: 18.8 -> 16.4 us per GroupNorm at 2 x 128 x 128 x 320 (profiles/r06_zh_probe_gn_fast_silu.log)
 MI_DEV float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }

@@ -147,7 +147,7 @@ extern "C" int mi355x_gemm(const mi355x_gemm_args* a, void* stream) {
     p.ld_rowbias = a->ld_rowbias;
     p.rows_per_group = a->rows_per_group > 0 ? a->rows_per_group : 1;
     p.geglu = a->geglu == 1 ? 1 : 0;
-    p.gelu = a->geglu == 2 ? 1 : (a->geglu == 3 ? 2 : (a->geglu == 4 ? 3 : 0));
+    p.gelu = a->geglu == 2 ? 1 : (a->geglu == 3 ? 2 : (a->geglu == 4 ? 3 : (a->geglu == 5 ? 4 : 0)));
     p.res = static_cast<const char*>(a->res);
     p.ldres = a->ldres;
     p.zeros = static_cast<const char*>(a->zeros);

@@ -32,7 +32,7 @@ struct GemmP {
     int64_t ld_rowbias;  // elements
     int rows_per_group;
     int geglu;
-    int gelu;  // activation on every output column (after bias / row bias, before the residual): 1 = erf-GELU, 2 = x * sigmoid(1.702 x), 3 = ReLU
+    int gelu;  // activation on every output column (after bias / row bias, before the residual): 1 = erf-GELU, 2 = x * sigmoid(1.702 x), 3 = ReLU, 4 = squared ReLU
     const char* res;
     int64_t ldres;  // elements
     const char* zeros;

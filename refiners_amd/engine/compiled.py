@@ -36,7 +36,7 @@ from ..fluxion.tree import tree_epoch
 from .packing import PackCache, Unsupported, isa, kids, launches  # noqa: F401
 from .unet_lowering import UNetIO, UNetLowering  # noqa: F401
 
-TOKEN_CONTEXTS = (("cross_attention_block", "clip_text_embedding"), ("ip_adapter", "clip_image_embedding"))
+TOKEN_CONTEXTS = (("cross_attention_block", "clip_text_embedding"), ("ip_adapter", "clip_image_embedding"), ("adapted_cross_attention_block", "llm_text_embedding"))
 
 
 def _ident(t: Optional[Tensor]) -> Any:
@@ -112,12 +112,21 @@ class CompiledUNet:
         self.lowerings, self.prologue_runs = 0, 0  # over this engine's life; shown in `stats` (a re-lowering replaces the dict, not the counts)
 
     # -- context plumbing ----------------------------------------------------------------------------------
+    def _tree(self) -> Any:
+        """The UNet itself when the engine was given the chain of an adapter that is the UNet's parent (ELLAAdapter = Chain(unet))."""
+        u = self.unet
+        if isa(u, "ELLAAdapter") and len(kids(u)) == 1:
+            u = kids(u)[0]
+        return u
+
     def _contexts(self) -> dict[str, dict[str, Any]]:
         # Chain.set_context REPLACES the top-level dict but MERGES into every descendant's (context.py:16-46,
         # chain.py:131-156; SURVEY.md appendix C), so after set_timestep / set_time_ids / ... only a child Chain sees
         # all of them -- read where the UseContext nodes read, not at unet.provider.
-        child = next((m for m in kids(self.unet) if isa(m, "Chain")), None)
-        return (child if child is not None else self.unet).provider.contexts
+        # (not at an ELLA encoder at index 0 either: it joined the tree at inject() and has seen only the contexts set since)
+        tree = self._tree()
+        child = next((m for m in kids(tree) if isa(m, "Chain") and not isa(m, "ELLA")), None)
+        return (child if child is not None else tree).provider.contexts
 
     def _gather(self) -> dict[str, Any]:
         c = self._contexts()
@@ -125,9 +134,10 @@ class CompiledUNet:
         got: dict[str, Any] = {"timestep": diff.get("timestep"), "pooled": diff.get("pooled_text_embedding"), "time_ids": diff.get("time_ids"), "tokens": {}, "conditions": {},
                                "t2i": {}}
         assert got["timestep"] is not None, "context diffusion.timestep is unset (call unet.set_timestep first)"
+        ella = any(isa(m, "ELLA") for m in kids(self._tree()))  # (its LLM embedding outlives an eject() in the context store: without the encoder nothing reads it)
         for ctx, key in TOKEN_CONTEXTS:
             v = c.get(ctx, {}).get(key)
-            if v is not None:
+            if v is not None and (ella or ctx != "adapted_cross_attention_block"):
                 got["tokens"][(ctx, key)] = v
         for name, d in c.items():
             if name.startswith("control_lora_") and d.get("condition") is not None:
@@ -173,7 +183,7 @@ class CompiledUNet:
         low.sag_capture = getattr(self, "sag_capture", True)
         low.style_half_batch = self.io_override is not None  # StyleAligned: this program is ONE half of the CFG pair, all its rows share row 0
         self.style_watch = low.style_modules  # (filled while lowering; kept when it raises Unsupported)
-        low.lower(self.unet, io)
+        low.lower(self._tree(), io)
         self.cache.sweep()
         # the step program is replayed step after step: let every GEMM / conv pull the weights of the launches behind it into
         # the Infinity Cache (weights are read exactly once per step, so otherwise every kernel starts on DRAM misses)
@@ -459,15 +469,16 @@ class CompiledSDXL:
 
     def set_inputs(self, x: Tensor, *, clip_text_embedding: Tensor, pooled_text_embedding: Optional[Tensor] = None, time_ids: Optional[Tensor] = None,
                    clip_image_embedding: Optional[Tensor] = None, conditions: Optional[dict[str, Tensor]] = None,
-                   t2i_features: Optional[dict[str, Any]] = None, generator: Optional[torch.Generator] = None) -> None:
+                   t2i_features: Optional[dict[str, Any]] = None, generator: Optional[torch.Generator] = None, llm_text_embedding: Optional[Tensor] = None) -> None:
         """x: (N, 4, H, W) initial latents; embeddings are [negative ; conditional] stacks of 2N rows;
         `conditions` maps a ControlLora name to its control image, (2N, 3, 8H, 8W) or ONE picture (1, 3, 8H, 8W) for the whole batch; `t2i_features` maps a T2I-Adapter name to
-        the tuple its `compute_condition_features` returned (batch 1 or 2N).
+        the tuple its `compute_condition_features` returned (batch 1 or 2N); `llm_text_embedding` (2N, T, width): the LLM's token embeddings an injected ELLA adapter reads
+        (ELLAAdapter.set_llm_text_embedding).
         With `classifier_free_guidance=False` there is no negative half: embeddings have N rows, pictures and features 1 or N."""
         if not self._cfg:
             n = x.shape[0]
             for what, t in (("clip_text_embedding", clip_text_embedding), ("pooled_text_embedding", pooled_text_embedding), ("time_ids", time_ids),
-                            ("clip_image_embedding", clip_image_embedding)):
+                            ("clip_image_embedding", clip_image_embedding), ("llm_text_embedding", llm_text_embedding)):
                 assert t is None or t.shape[0] == n, f"classifier_free_guidance=False: {what} has {t.shape[0]} rows, the latents have {n} (no [negative ; conditional] stack)"
             for what, t in [(k, v) for k, v in (conditions or {}).items()] + [(k, f) for k, feats in (t2i_features or {}).items() for f in feats]:
                 assert t.shape[0] in (1, n), f"classifier_free_guidance=False: condition '{what}' has {t.shape[0]} rows, expected 1 or {n}"
@@ -476,6 +487,8 @@ class CompiledSDXL:
         tokens = {("cross_attention_block", "clip_text_embedding"): clip_text_embedding}
         if clip_image_embedding is not None:
             tokens[("ip_adapter", "clip_image_embedding")] = clip_image_embedding
+        if llm_text_embedding is not None:
+            tokens[("adapted_cross_attention_block", "llm_text_embedding")] = llm_text_embedding
         self.inputs = {"pooled": pooled_text_embedding, "time_ids": time_ids, "tokens": tokens,
                        "conditions": {f"control_lora_{k}": v for k, v in (conditions or {}).items()},
                        "t2i": {k: tuple(v) for k, v in (t2i_features or {}).items()}}

@@ -362,15 +362,23 @@ class BlockLowering(Lowering):
     def cross_attention(self, x: Tensor, B: int, ln: Any, par: Any, att: Any, ctx: "UNetContext", stats: Optional[Tensor] = None,
                         stats_out: Optional[Tensor] = None) -> Tensor:
         """x += Wo (SDPA(Wq LN(x), K_text, V_text) [+ s SDPA(q, K_img, V_img)])   (cross_attention.py:50-68,
-        image_prompt.py:237-309).  K / V^T of the text and image tokens are produced in the prologue."""
+        image_prompt.py:237-309).  K / V^T of the text and image tokens are produced in the prologue; those of a token stream the step
+        itself produces (ELLA's latents: `step_tokens`) in the step, pinned for the rest of it."""
         pc = kids(par)
+        adapted = len(pc) == 3 and all(isa(c, "ELLACrossAttentionAdapter") for c in pc[1:])
+        if adapted:  # ELLACrossAttentionAdapter = Chain(UseContext ella.latents) in place of the bare UseContext (ella_adapter.py:249-253)
+            _expect(all(len(kids(c)) == 1 for c in pc[1:]), "unexpected ELLACrossAttentionAdapter layout")
+            pc = [pc[0]] + [kids(c)[0] for c in pc[1:]]
         _expect(len(pc) == 3 and isa(pc[0], "Identity") and all(isa(c, "UseContext") for c in pc[1:]), "unexpected cross-attention Parallel")
         _expect(pc[1].context == pc[2].context and pc[1].key == pc[2].key, "key and value read different contexts")
         (qn, kn, vn), sd, on, ip = self._split_attention(att)
         heads = sd.num_heads
         src, Lk = ctx.tokens(pc[1].context, pc[1].key)
-        with self.in_prologue():
+        in_step = (pc[1].context, pc[1].key) in getattr(self, "step_tokens", ())
+        with (self.in_step() if in_step else self.in_prologue()):
             k, v_or_vt, v_plain = self.project_kv(src, B, kn, vn, heads)
+        if adapted:
+            self.stats["ella_sites"] = self.stats.get("ella_sites", 0) + 1
         streams = [(k, v_or_vt, Lk, 1.0)]
         plains = [v_plain]
         if ip is not None:

@@ -13,6 +13,7 @@ from torch import Tensor, nn
 
 from .. import native
 
+from .ella import EllaLowering
 from .lowering_blocks import BlockLowering
 from .packing import Act, CatAct, ConvSpec, LinSpec, LoraPack, PackCache, Pool, Unsupported, _expect, cname, isa, kids, launches  # noqa: F401
 
@@ -83,9 +84,9 @@ class UNetIO:
     t2i: dict[str, list[Tensor]] = field(default_factory=dict)  # T2I-Adapter name -> its feature maps, NCHW, batch 1 or B
 
 
-class UNetLowering(BlockLowering):
+class UNetLowering(EllaLowering, BlockLowering):
     """Lowers SDXLUNet / SD1UNet trees (reference xl/unet.py:258-351, sd1/unet.py:165-249), with ControlLoras at
-    index 0 (xl/control_lora.py:144-248), into `prologue` + `step`."""
+    index 0 (xl/control_lora.py:144-248) or an ELLA latents encoder there (latent_diffusion/ella_adapter.py:212-292, engine/ella.py), into `prologue` + `step`."""
 
     def lower(self, unet: Any, io: UNetIO) -> None:
         B, _, H, W = io.x.shape
@@ -94,6 +95,7 @@ class UNetLowering(BlockLowering):
         ctx.text = dict(io.tokens)
         n_slots = len(unet.init_context()["unet"]["residuals"])
         ctx.residuals = [None] * n_slots
+        self.step_tokens = set()  # (context, key) of the token streams the step itself produces: their K / V^T projections are step work
         cur: Any = None
         with self.in_step():
             for child in kids(unet):
@@ -101,6 +103,8 @@ class UNetLowering(BlockLowering):
                     self.control_lora(child, ctx, H, W)
                 elif isa(child, "Controlnet"):
                     self.controlnet(child, ctx, H, W)
+                elif isa(child, "ELLA"):
+                    self.ella_child(child, ctx)
                 elif isa(child, "TimestepEncoder"):
                     self.timestep_encoder(child, ctx, scope=unet)
                 elif cname(child) in ("DownBlocks", "UpBlocks"):

@@ -1,0 +1,1 @@
+from .ella import ELLA, ELLAAdapter, SD1ELLAAdapter  # noqa: F401

@@ -69,6 +69,10 @@ globals().update({cls.__name__: cls for cls in _abi_mvanet.structs.values()})
 DINOV2_STRUCT_NAMES = {"mi355x_dinov2_pos_resample_args": "Dinov2PosResampleArgs", "mi355x_dinov2_tokens_args": "Dinov2TokensArgs"}
 _abi_dinov2 = abi.read(DINOV2_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_dinov2.h")
 globals().update({cls.__name__: cls for cls in _abi_dinov2.structs.values()})
+#: include/mi355x_refiners_ella.h, the AdaLayerNorm pass of ELLA's Perceiver resampler
+ELLA_STRUCT_NAMES = {"mi355x_ella_adaln_args": "EllaAdaLnArgs"}
+_abi_ella = abi.read(ELLA_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_ella.h")
+globals().update({cls.__name__: cls for cls in _abi_ella.structs.values()})
 _K = _abi.constants
 
 #: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
@@ -83,6 +87,8 @@ EXPORTS_SWIN = list(_abi_swin.functions)
 EXPORTS_MVANET = list(_abi_mvanet.functions)
 #: every symbol include/mi355x_refiners_dinov2.h declares
 EXPORTS_DINOV2 = list(_abi_dinov2.functions)
+#: every symbol include/mi355x_refiners_ella.h declares
+EXPORTS_ELLA = list(_abi_ella.functions)
 #: exported for probing and A/B runs, by design not in the header (no stable contract): name -> (restype, argtypes), applied by load() like the header's
 UNSTABLE = {
     "mi355x_set_option": (C.c_int, [C.c_char_p, C.c_int]),
@@ -178,7 +184,7 @@ def load(path: Optional[Path] = None) -> C.CDLL:
         lib = C.CDLL(str(p))
     except OSError as e:  # e.g. no HIP runtime on this machine
         raise NativeError(f"cannot load {p}: {e}") from e
-    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **_abi_mvanet.functions, **_abi_dinov2.functions, **UNSTABLE}.items():
+    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **_abi_mvanet.functions, **_abi_dinov2.functions, **_abi_ella.functions, **UNSTABLE}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.mi355x_abi_version() != ABI_VERSION:
@@ -505,6 +511,7 @@ def gemm(
     geglu: bool = False,
     gelu: bool = False,
     relu: bool = False,
+    squared_relu: bool = False,
     M: Optional[int] = None,
     N: Optional[int] = None,
     tile: int = 0,
@@ -546,7 +553,7 @@ def gemm(
         sg.x, sg.ldx, sg.w, sg.ldw, sg.k = t[0].data_ptr(), t[1], t[2].data_ptr(), t[3], t[4]
         sg.ksize, sg.stride, sg.ups, sg.H, sg.W, sg.kblocked = 1, 1, 1, 0, 0, t[5]
         keep.append((x, w))
-    assert int(bool(geglu)) + int(bool(gelu)) + int(relu) <= 1
+    assert int(bool(geglu)) + int(bool(gelu)) + int(relu) + int(squared_relu) <= 1
     if out_t is not None:
         assert out_t.dim() == 2 and out_t.stride(1) == 1 and out_t.shape[0] >= a.N - nt_begin and out_t.shape[1] >= a.M
         a.out_t, a.ldt, a.nt_begin = out_t.data_ptr(), out_t.stride(0), nt_begin
@@ -556,7 +563,7 @@ def gemm(
         a.bias = bias.data_ptr() if bias is not None else None
         a.rowbias, a.ld_rowbias, a.rows_per_group, a.res, a.ldres, a.geglu = None, 0, 1, None, 0, 0
     else:
-        _fill_epilogue(a, out, bias, rowbias, rows_per_group, res, (3 if gelu == "quick" else 2) if gelu else (4 if relu else geglu))
+        _fill_epilogue(a, out, bias, rowbias, rows_per_group, res, (3 if gelu == "quick" else 2) if gelu else (4 if relu else (5 if squared_relu else geglu)))
     if out_f32:
         assert out is not None and out.dtype == torch.float32
         a.out_f32 = 1
@@ -806,7 +813,7 @@ def _fill_epilogue(a: GemmArgs, out: Tensor, bias, rowbias, rows_per_group, res,
         a.res, a.ldres = res.data_ptr(), res.stride(0)
     else:
         a.res, a.ldres = None, 0
-    a.geglu = int(geglu)  # 0 none, 1 GEGLU, 2 GELU (erf), 3 quick GELU, 4 ReLU
+    a.geglu = int(geglu)  # 0 none, 1 GEGLU, 2 GELU (erf), 3 quick GELU, 4 ReLU, 5 squared ReLU
 
 
 def attention(
@@ -1293,6 +1300,31 @@ def dinov2_tokens(patch: Tensor, pos: Tensor, cls: Tensor, pos0: Tensor, reg: Op
     a.reg, a.ldr = (reg.data_ptr(), reg.stride(0)) if reg is not None else (None, 0)
     a.out, a.ldo = out.data_ptr(), out.stride(0)
     _launch("mi355x_dinov2_tokens", (C.byref(a),), "mi355x_dinov2_tokens", keep=(pos, cls, pos0, reg))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ ELLA's resampler (csrc/ella.hip)
+def ella_adaln(latents: Tensor, shift_l: Tensor, scale_l: Tensor, out: Tensor, x: Optional[Tensor] = None, shift_x: Optional[Tensor] = None,
+               scale_x: Optional[Tensor] = None, eps: float = 1e-6) -> Tensor:
+    """mi355x_ella_adaln: out [B, Lp, C] <- [LN0(latents) * (1 + scale_l) + shift_l ; LN0(x) * (1 + scale_x) + shift_x ; zero rows].
+    latents [B, Nl, C], x [B, T, C] or None (the feed-forward form), out [B, Lp >= Nl + T, C]: 3-D views with a contiguous last dimension.
+    shift_* / scale_* [B, C]: 2-D views of one row stride (column slices of the time table)."""
+    a = EllaAdaLnArgs()
+    B, Nl, C_ = latents.shape
+    T = 0 if x is None else x.shape[1]
+    mods = [shift_l, scale_l] + ([shift_x, scale_x] if T else [])
+    assert out.dim() == 3 and out.shape[0] == B and out.shape[2] == C_ and latents.stride(2) == 1 and out.stride(2) == 1
+    assert all(m is not None and tuple(m.shape) == (B, C_) and m.stride(1) == 1 and m.stride(0) == shift_l.stride(0) and m.dtype == latents.dtype for m in mods)
+    a.dtype = dtype_code(latents.dtype)
+    a.B, a.Nl, a.T, a.Lp, a.C = B, Nl, T, out.shape[1], C_
+    a.latents, a.ldl, a.l_batch_stride = latents.data_ptr(), latents.stride(1), latents.stride(0)
+    if T:
+        assert x.dim() == 3 and x.shape[0] == B and x.shape[2] == C_ and x.stride(2) == 1 and x.dtype == latents.dtype
+        a.x, a.ldx, a.x_batch_stride = x.data_ptr(), x.stride(1), x.stride(0)
+        a.shift_x, a.scale_x = shift_x.data_ptr(), scale_x.data_ptr()
+    a.shift_l, a.scale_l, a.mod_batch_stride, a.eps = shift_l.data_ptr(), scale_l.data_ptr(), shift_l.stride(0), eps
+    a.out, a.ldo, a.out_batch_stride = out.data_ptr(), out.stride(1), out.stride(0)
+    _launch("mi355x_ella_adaln", (C.byref(a),), "mi355x_ella_adaln", keep=(latents, x, shift_l, scale_l, shift_x, scale_x, out))
     return out
 
 
