@@ -119,6 +119,20 @@ class LayerNorm2d(WeightedModule):
         return self.weight[:, None, None] * ((x - mu) / torch.sqrt(var + self.eps)) + self.bias[:, None, None]
 
 
+class InstanceNorm2d(nn.InstanceNorm2d, Module):
+    """Per-image, per-channel normalisation with no affine and no running statistics (reference: fluxion/layers/norm.py:130-154)."""
+
+    def __init__(self, num_features: int, eps: float = 1e-05, device: Any = None, dtype: Any = None) -> None:
+        super().__init__(num_features=num_features, eps=eps, device=device, dtype=dtype)
+
+
+class ReflectionPad2d(nn.ReflectionPad2d, Module):
+    """reference: fluxion/layers/padding.py:6-19."""
+
+    def __init__(self, padding: int) -> None:
+        super().__init__(padding=padding)
+
+
 class Parameter(WeightedModule):
     def __init__(self, *dims: int, requires_grad: bool = True, device: Any = None, dtype: Any = None) -> None:
         super().__init__()

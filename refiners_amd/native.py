@@ -73,6 +73,11 @@ globals().update({cls.__name__: cls for cls in _abi_dinov2.structs.values()})
 ELLA_STRUCT_NAMES = {"mi355x_ella_adaln_args": "EllaAdaLnArgs"}
 _abi_ella = abi.read(ELLA_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_ella.h")
 globals().update({cls.__name__: cls for cls in _abi_ella.structs.values()})
+#: include/mi355x_refiners_lineart.h, the stem, InstanceNorm2d passes and head of the InformativeDrawings preprocessor
+LINEART_STRUCT_NAMES = {"mi355x_lineart_stem_args": "LineartStemArgs", "mi355x_lineart_in_stats_args": "LineartInStatsArgs",
+                        "mi355x_lineart_in_apply_args": "LineartInApplyArgs", "mi355x_lineart_head_args": "LineartHeadArgs"}
+_abi_lineart = abi.read(LINEART_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_lineart.h")
+globals().update({cls.__name__: cls for cls in _abi_lineart.structs.values()})
 _K = _abi.constants
 
 #: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
@@ -89,6 +94,8 @@ EXPORTS_MVANET = list(_abi_mvanet.functions)
 EXPORTS_DINOV2 = list(_abi_dinov2.functions)
 #: every symbol include/mi355x_refiners_ella.h declares
 EXPORTS_ELLA = list(_abi_ella.functions)
+#: every symbol include/mi355x_refiners_lineart.h declares
+EXPORTS_LINEART = list(_abi_lineart.functions)
 #: exported for probing and A/B runs, by design not in the header (no stable contract): name -> (restype, argtypes), applied by load() like the header's
 UNSTABLE = {
     "mi355x_set_option": (C.c_int, [C.c_char_p, C.c_int]),
@@ -184,7 +191,7 @@ def load(path: Optional[Path] = None) -> C.CDLL:
         lib = C.CDLL(str(p))
     except OSError as e:  # e.g. no HIP runtime on this machine
         raise NativeError(f"cannot load {p}: {e}") from e
-    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **_abi_mvanet.functions, **_abi_dinov2.functions, **_abi_ella.functions, **UNSTABLE}.items():
+    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **_abi_mvanet.functions, **_abi_dinov2.functions, **_abi_ella.functions, **_abi_lineart.functions, **UNSTABLE}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.mi355x_abi_version() != ABI_VERSION:
@@ -1333,6 +1340,95 @@ def glu_silu(x: Tensor, out: Tensor) -> Tensor:
     M, F2 = x.shape
     assert x.dim() == 2 and F2 % 2 == 0 and tuple(out.shape) == (M, F2 // 2) and x.stride(1) == out.stride(1) == 1 and x.dtype == out.dtype
     _launch("mi355x_glu_silu", (dtype_code(x.dtype), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), M, F2 // 2), "mi355x_glu_silu")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ InformativeDrawings (csrc/lineart.hip)
+LINEART_ROWS, LINEART_PADDED, LINEART_QUAD = (_abi_lineart.constants[f"MI355X_LINEART_{n}"] for n in ("ROWS", "PADDED", "QUAD"))
+LINEART_MAX_CIN = _abi_lineart.constants["MI355X_LINEART_MAX_CIN"]
+
+
+def lineart_rows(B: int, H: int, W: int, layout: int = LINEART_ROWS, pad: int = 0) -> int:
+    """Rows of the buffer that holds a logical [B, H, W] activation in `layout` (include/mi355x_refiners_lineart.h)."""
+    if layout == LINEART_QUAD:
+        return B * (H // 2) * (W // 2)
+    return B * (H + 2 * pad) * (W + 2 * pad)
+
+
+def _lineart_src(a: Any, x: Tensor, B: int, H: int, W: int, C_: int, layout: int, pad: int) -> None:
+    cols = 4 * C_ if layout == LINEART_QUAD else C_
+    assert x.dim() == 2 and x.stride(1) == 1 and x.shape[0] == lineart_rows(B, H, W, layout, pad) and x.shape[1] >= cols, "activation of another shape than its layout"
+    a.dtype, a.B, a.H, a.W, a.layout, a.pad, a.x, a.ldx = dtype_code(x.dtype), B, H, W, layout, pad, x.data_ptr(), x.stride(0)
+
+
+def lineart_pack_stem(w: Tensor) -> Tensor:
+    """Conv2d weight [64, Cin, 7, 7] -> float32 [Cin * 49, 64] (row (ci 7 + ky) 7 + kx, column co), as mi355x_lineart_stem reads it."""
+    o, i, kh, kw = w.shape
+    assert (o, kh, kw) == (64, 7, 7)
+    return w.detach().float().permute(1, 2, 3, 0).reshape(i * 49, 64).contiguous()
+
+
+def lineart_pack_head(w: Tensor) -> Tensor:
+    """Conv2d weight [1, 64, 7, 7] -> float32 [49, 64] (row 7 ky + kx, column ci), as mi355x_lineart_head reads it."""
+    assert tuple(w.shape) == (1, 64, 7, 7)
+    return w.detach().float()[0].permute(1, 2, 0).reshape(49, 64).contiguous()
+
+
+def lineart_stem(image: Tensor, w: Tensor, bias: Optional[Tensor], out: Tensor) -> Tensor:
+    """out [B * H * W, >= 64] rows = Conv2d(Cin -> 64, 7)(ReflectionPad2d(3)(image [B, Cin, H, W])); w = lineart_pack_stem(weight), bias float32 [64] or None."""
+    B, Cin, H, W = image.shape
+    assert image.stride(3) == 1 and image.dtype == out.dtype and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == B * H * W and out.shape[1] >= 64
+    assert w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (Cin * 49, 64) and (bias is None or (bias.dtype == torch.float32 and bias.numel() == 64 and bias.is_contiguous()))
+    a = LineartStemArgs()
+    a.dtype, a.B, a.H, a.W, a.Cin = dtype_code(image.dtype), B, H, W, Cin
+    a.image, a.batch_stride, a.channel_stride, a.row_stride = image.data_ptr(), image.stride(0), image.stride(1), image.stride(2)
+    a.w, a.bias = w.data_ptr(), None if bias is None else bias.data_ptr()
+    a.out, a.ldo = out.data_ptr(), out.stride(0)
+    _launch("mi355x_lineart_stem", (C.byref(a),), "mi355x_lineart_stem", keep=(image, w, bias, out))
+    return out
+
+
+def lineart_in_stats_ws_floats(B: int, H: int, W: int, C_: int, layout: int = LINEART_ROWS) -> int:
+    return int(load().mi355x_lineart_in_stats_ws_floats(B, H, W, C_, layout))
+
+
+def lineart_in_stats(x: Tensor, B: int, H: int, W: int, C_: int, eps: float, stats: Tensor, layout: int = LINEART_ROWS, pad: int = 0, ws: Optional[Tensor] = None) -> Tensor:
+    """stats float32 [B, C_, 2] = (mean, 1 / sqrt(biased variance + eps)) per image and channel of the logical [B, H, W, C_] activation x."""
+    assert stats.dtype == torch.float32 and tuple(stats.shape) == (B, C_, 2) and stats.is_contiguous()
+    a = LineartInStatsArgs()
+    _lineart_src(a, x, B, H, W, C_, layout, pad)
+    if ws is None:
+        ws = torch.empty(max(lineart_in_stats_ws_floats(B, H, W, C_, layout), 4) if x.device.type != "meta" else 4, device=x.device, dtype=torch.float32)
+    assert ws.dtype == torch.float32 and ws.is_contiguous()
+    a.C, a.eps, a.stats, a.ws, a.ws_floats = C_, eps, stats.data_ptr(), ws.data_ptr(), ws.numel()
+    _launch("mi355x_lineart_in_stats", (C.byref(a),), "mi355x_lineart_in_stats", keep=(x, stats, ws))
+    return stats
+
+
+def lineart_in_apply(x: Tensor, B: int, H: int, W: int, C_: int, stats: Tensor, out: Tensor, layout: int = LINEART_ROWS, pad: int = 0, relu: bool = False,
+                     res: Optional[Tensor] = None, res_pad: int = 0, ring: int = 0) -> Tensor:
+    """out = (x - mean) rstd [ReLU] [+ interior of res], written as rows of (H + 2 ring) x (W + 2 ring) images whose ring is ReflectionPad2d(ring)."""
+    assert stats.dtype == torch.float32 and tuple(stats.shape) == (B, C_, 2) and stats.is_contiguous()
+    assert out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == lineart_rows(B, H, W, LINEART_PADDED, ring) and out.shape[1] >= C_ and out.dtype == x.dtype
+    a = LineartInApplyArgs()
+    _lineart_src(a, x, B, H, W, C_, layout, pad)
+    a.C, a.stats, a.relu, a.ring, a.out, a.ldo = C_, stats.data_ptr(), int(relu), ring, out.data_ptr(), out.stride(0)
+    if res is not None:
+        assert res.dim() == 2 and res.stride(1) == 1 and res.shape[0] == lineart_rows(B, H, W, LINEART_PADDED, res_pad) and res.shape[1] >= C_ and res.dtype == x.dtype
+        a.res, a.ldr, a.res_pad = res.data_ptr(), res.stride(0), res_pad
+    _launch("mi355x_lineart_in_apply", (C.byref(a),), "mi355x_lineart_in_apply", keep=(x, stats, res, out))
+    return out
+
+
+def lineart_head(x: Tensor, B: int, H: int, W: int, stats: Tensor, w: Tensor, bias: float, out: Tensor, layout: int = LINEART_ROWS, pad: int = 0) -> Tensor:
+    """out [B, 1, H, W] = Sigmoid(Conv2d(64 -> 1, 7)(ReflectionPad2d(3)(ReLU(InstanceNorm2d(x)))) + bias); w = lineart_pack_head(weight)."""
+    assert stats.dtype == torch.float32 and tuple(stats.shape) == (B, 64, 2) and stats.is_contiguous()
+    assert w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (49, 64)
+    assert out.dim() == 4 and tuple(out.shape) == (B, 1, H, W) and out.stride(3) == 1 and out.stride(2) == W and out.dtype == x.dtype
+    a = LineartHeadArgs()
+    _lineart_src(a, x, B, H, W, 64, layout, pad)
+    a.stats, a.w, a.bias, a.out, a.out_batch_stride = stats.data_ptr(), w.data_ptr(), float(bias), out.data_ptr(), out.stride(0)
+    _launch("mi355x_lineart_head", (C.byref(a),), "mi355x_lineart_head", keep=(x, stats, w, out))
     return out
 
 
