@@ -18,7 +18,7 @@ reference's own convention for unknown children -- the stock child loop runs (fl
 "unsupported => fall back, never error") -- at two levels, both reported: a context-free sub-tree inside a UNet stage runs through its own
 torch forward inside the recorded program (`.stats["fallback_nodes"]`); anything else (a node that needs the Chain's context store at run
 time, an unknown top-level layout) makes the WHOLE call run `unet(x)`, with a `RuntimeWarning` naming the reason and
-`.stats["whole_fallback"]` set.  Adapters outside SURVEY.md section 8 (FreeU, reference-only ...) therefore keep working, unfused.
+`.stats["whole_fallback"]` set.  Adapters outside SURVEY.md section 8 (FreeU ...) therefore keep working, unfused.
 StyleAlignedAdapter is lowered (`.stats["style_aligned_sites"]`): its scale lives in device memory and is refreshed before every replay.
 """
 from __future__ import annotations
@@ -101,10 +101,12 @@ class CompiledUNet:
         self.io: Optional[UNetIO] = None
         self.key: Any = None
         self.bad_key: Any = None  # the (tree state, geometry) key whose lowering raised Unsupported: those calls run the stock forward
-        # StyleAligned's ScaleReferenceFeatures of the tree as the last lowering met them, and their scales when the tree was last refused: assigning a
-        # scale bumps no tree epoch (the lowered program reads it from device memory), so a refusal is retried when these values moved
+        # the modules whose live attributes the lowered program reads from device memory, as the last lowering met them -- StyleAligned's ScaleReferenceFeatures
+        # (`scale`) and reference-only control's SelfAttentionInjectionAdapters (`style_cfg`) -- and their values when the tree was last refused: assigning one
+        # bumps no tree epoch, so a refusal is retried when these values moved
         self.style_watch: list = []
-        self.bad_scales: Any = None
+        self.ro_watch: list = []
+        self.bad_values: Any = None
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.prologue_key: Any = None
         self.prologue_refs: Any = None  # the staged source tensors themselves (see _ident)
@@ -123,10 +125,14 @@ class CompiledUNet:
         # Chain.set_context REPLACES the top-level dict but MERGES into every descendant's (context.py:16-46,
         # chain.py:131-156), so after set_timestep / set_time_ids / ... only a child Chain sees
         # all of them -- read where the UseContext nodes read, not at unet.provider.
-        # (not at an ELLA encoder at index 0 either: it joined the tree at inject() and has seen only the contexts set since)
+        # (not at an ELLA encoder or a reference-only guide pass at index 0 either: they joined the tree at inject() and have seen only the contexts set since)
         tree = self._tree()
-        child = next((m for m in kids(tree) if isa(m, "Chain") and not isa(m, "ELLA")), None)
+        child = next((m for m in kids(tree) if isa(m, "Chain") and not isa(m, "ELLA", "SelfAttentionInjectionPassthrough")), None)
         return (child if child is not None else tree).provider.contexts
+
+    def reference_only(self) -> bool:
+        """The tree carries reference-only control: its guide pass is the UNet's first child."""
+        return any(isa(m, "SelfAttentionInjectionPassthrough") for m in kids(self._tree())[:1])
 
     def _gather(self) -> dict[str, Any]:
         c = self._contexts()
@@ -146,6 +152,8 @@ class CompiledUNet:
                 for key, v in d.items():
                     if key.startswith("condition_") and v is not None:
                         got["conditions"][f"controlnet.{key}"] = v
+        if self.reference_only():  # (the guide outlives an eject() in the context store)
+            got["guide"] = c.get("reference_only_control", {}).get("guide")  # a STEP input: read and copied on every call
         for key, feats in c.get("t2iadapter", {}).items():  # T2IAdapter.set_condition_features (t2i_adapter.py:201-202)
             if key.startswith("condition_features_") and feats is not None:
                 got["t2i"][key.removeprefix("condition_features_")] = tuple(feats)
@@ -179,11 +187,16 @@ class CompiledUNet:
             io.conditions[name] = torch.empty(tuple(v.shape), device=dev, dtype=dtype)
         for name, feats in got.get("t2i", {}).items():
             io.t2i[name] = [torch.empty(tuple(f.shape), device=dev, dtype=dtype) for f in feats]
+        if got.get("guide") is not None:
+            io.guide = torch.empty(tuple(got["guide"].shape), device=dev, dtype=dtype)
         low = UNetLowering(dev, dtype, self.cache, self.lora_mode)
         low.sag_capture = getattr(self, "sag_capture", True)
         low.style_half_batch = self.io_override is not None  # StyleAligned: this program is ONE half of the CFG pair, all its rows share row 0
         self.style_watch = low.style_modules  # (filled while lowering; kept when it raises Unsupported)
-        low.lower(self._tree(), io)
+        try:
+            low.lower(self._tree(), io)
+        finally:
+            self.ro_watch = getattr(low, "ro_adapters", [])
         self.cache.sweep()
         # the step program is replayed step after step: let every GEMM / conv pull the weights of the launches behind it into
         # the Infinity Cache (weights are read exactly once per step, so otherwise every kernel starts on DRAM misses)
@@ -208,6 +221,8 @@ class CompiledUNet:
         io.timestep.copy_(ts.expand(io.timestep.shape[0]) if ts.numel() == 1 else ts)
         if io.step_rows is not None:
             io.step_rows.copy_(self.rows_table[int(got["step_index"])])
+        if io.guide is not None:
+            io.guide.copy_(got["guide"])
         lcm = getattr(self.low, "lcm_scale", None)  # SDXLLcmAdapter's condition scale: a prologue input (UNetLowering._fold_condition_scale)
         pk = (_ident(got.get("timesteps_all")), _ident(got["pooled"]), _ident(got["time_ids"]), tuple(_ident(v) for v in got["tokens"].values()), tuple(_ident(v) for v in got["conditions"].values()),
               tuple(_ident(f) for feats in got.get("t2i", {}).values() for f in feats), None if lcm is None else lcm())
@@ -266,8 +281,9 @@ class CompiledUNet:
         key = (self._tree_state(), tuple(x_shape), self.unet.dtype, None if got.get("timesteps_all") is None else int(got["timesteps_all"].numel()),
                tuple((k, tuple(v.shape)) for k, v in got["tokens"].items()),
                tuple((k, tuple(v.shape)) for k, v in got["conditions"].items()), got["pooled"] is not None,
-               tuple((k, tuple(tuple(f.shape) for f in feats)) for k, feats in got.get("t2i", {}).items()), self.io_override is not None)
-        if key == self.bad_key and self.bad_scales != self._style_scales():
+               tuple((k, tuple(tuple(f.shape) for f in feats)) for k, feats in got.get("t2i", {}).items()), self.io_override is not None,
+               None if got.get("guide") is None else tuple(got["guide"].shape))
+        if key == self.bad_key and self.bad_values != self._live_values():
             self.bad_key = None  # a StyleAligned scale was assigned since the refusal: look at the tree again
         if key != self.key:
             if key == self.bad_key:
@@ -276,9 +292,9 @@ class CompiledUNet:
                 self._build(x_shape, device, got)
             except Unsupported as exc:
                 # remembered per (tree state, geometry): the next call does not walk the tree again; any inject / eject / scale change retries
-                # (StyleAligned scales bump no epoch: they are compared by value, see bad_scales)
+                # (StyleAligned scales and reference-only style_cfg bump no epoch: they are compared by value, see bad_values)
                 self.bad_key, self.key, self.low, self.io, self.graph = key, None, None, None, None
-                self.bad_scales = self._style_scales()
+                self.bad_values = self._live_values()
                 self.stats = {"whole_fallback": str(exc), "fallback_nodes": ["<whole UNet>"], "step_ops": 0, "prologue_ops": 0}
                 warnings.warn(f"refiners_amd: this UNet tree is not lowered to the MI355X kernels ({exc}); running the stock Chain forward instead", RuntimeWarning, stacklevel=3)
                 raise
@@ -286,8 +302,8 @@ class CompiledUNet:
         self._refresh_style_scale(key)
         return self._stage_inputs(got)
 
-    def _style_scales(self) -> tuple:
-        return tuple(float(m.scale) for m in self.style_watch)
+    def _live_values(self) -> tuple:
+        return tuple(float(m.scale) for m in self.style_watch) + tuple(float(m.style_cfg) for m in self.ro_watch)
 
     def _refresh_style_scale(self, key: Any) -> None:
         """StyleAligned's scale is a live attribute of the tree and the step is a captured graph: the kernels read it from one float in device
@@ -295,20 +311,31 @@ class CompiledUNet:
         scale; a tree whose ScaleReferenceFeatures were set apart by hand is no longer that pattern and is refused like any other tree the
         lowering does not know (stock forward behind the warning, retried once the scales change again)."""
         low = self.low
+        if low is not None and low.ro_mix is not None:  # reference-only control: the same arrangement for `style_cfg` (ro_mix = [style_cfg, 1])
+            cfgs = {float(m.style_cfg) for m in low.ro_adapters}
+            if len(cfgs) != 1:
+                self._refuse(key, "the self-attention injections of one UNet carry different style_cfg")
+            v = cfgs.pop()
+            if v != low.ro_mix_value:
+                low.ro_mix[:1].fill_(v)
+                low.ro_mix_value = v
         if low is None or not low.style_modules:
             return
-        vals = set(self._style_scales())
+        vals = set(float(m.scale) for m in self.style_watch)
         if len(vals) != 1:
-            why = "the StyleAligned layers carry different scales"
-            self.bad_key, self.key, self.low, self.io, self.graph = key, None, None, None, None
-            self.bad_scales = self._style_scales()
-            self.stats = {"whole_fallback": why, "fallback_nodes": ["<whole UNet>"], "step_ops": 0, "prologue_ops": 0}
-            warnings.warn(f"refiners_amd: this UNet tree is not lowered to the MI355X kernels ({why}); running the stock Chain forward instead", RuntimeWarning, stacklevel=4)
-            raise Unsupported(why)
+            self._refuse(key, "the StyleAligned layers carry different scales")
         v = vals.pop()
         if v != low.style_scale_value:
             low.style_scale.fill_(v)
             low.style_scale_value = v
+
+    def _refuse(self, key: Any, why: str) -> None:
+        """A live attribute moved the tree out of the lowered pattern: the stock forward behind the warning, retried once the values change again."""
+        self.bad_key, self.key, self.low, self.io, self.graph = key, None, None, None, None
+        self.bad_values = self._live_values()
+        self.stats = {"whole_fallback": why, "fallback_nodes": ["<whole UNet>"], "step_ops": 0, "prologue_ops": 0}
+        warnings.warn(f"refiners_amd: this UNet tree is not lowered to the MI355X kernels ({why}); running the stock Chain forward instead", RuntimeWarning, stacklevel=5)
+        raise Unsupported(why)
 
     def run_prologue(self) -> None:
         assert self.low is not None
@@ -516,6 +543,8 @@ class CompiledSDXL:
     def _split_wanted(self, n: int) -> bool:
         if not self._cfg or self._sag_adapter() is not None or self.x is None or self.x.device.type != "cuda":
             return False
+        if self.cfg_split is None and self.engine.reference_only():
+            return False  # reference-only control blends row 0 of the pair with the guide's keys: one program (an explicit cfg_split=True is refused by the lowering)
         return self.cfg_split if self.cfg_split is not None else n <= self.SPLIT_MAX_IMAGES
 
     def _split_got(self, got: dict[str, Any], n: int) -> tuple[dict[str, Any], dict[str, Any]]:
@@ -663,6 +692,8 @@ class CompiledSDXL:
             self._tables(self.x.device)  # condition_scale / solver changed since the last call
         eng = self.engine
         got = dict(self.inputs, timestep=self.ts_table[step : step + 1], timesteps_all=self.ts_table, step_index=step)
+        if eng.reference_only():  # the guide is noised per step by the caller (ReferenceOnlyControlAdapter.set_controlnet_condition): read on every call
+            got["guide"] = eng._contexts().get("reference_only_control", {}).get("guide")
         n = self.x.shape[0]
         if self._split_wanted(n):
             return self._split_step(step, got, n)

@@ -252,6 +252,9 @@ class BlockLowering(Lowering):
         """x += Wo SDPA(Wq h, Wk h, Wv h), h = LN(x)   (cross_attention.py:44-49; attentions.py:319-385).
         `stats`: row statistics of x (LayerNorm then runs inside the projection launches); `stats_out`: buffer for the
         statistics of the updated x."""
+        ro = None  # reference-only control (engine/reference_only.py): ("save", site, adapter) in the guide pass, ("inject", site, adapter) in the real one
+        if isa(att, "SaveLayerNormAdapter", "SelfAttentionInjectionAdapter"):
+            att, ro = self.reference_only_site(att)
         att, inserted, shared = self._style_aligned(att)
         (qn, kn, vn), sd, on, ip = self._split_attention(att, skip=inserted)
         _expect(ip is None, "image cross-attention on a self-attention")
@@ -263,8 +266,13 @@ class BlockLowering(Lowering):
         M, C = x.shape
         native_path = self.head_kernel(C // heads) is not None
         _expect(shared is None or native_path, f"StyleAligned on heads of {C // heads} channels, which no flash kernel serves")
+        _expect(ro is None or native_path, f"reference-only control on heads of {C // heads} channels, which no instance of the joint attention kernel serves")
+        _expect(ro is None or shared is None, "reference-only control on a StyleAligned shared self-attention is not lowered")
+        _expect(ro is None or tap is None, "reference-only control on a self-attention that Self-Attention Guidance taps is not lowered")
         L = M // B
         fold = self.ln_fusable(stats, qs, ks, vs)
+        if ro is not None and ro[0] == "save" and ro[1] == self.ro_last:
+            self.reference_only_last(ro[1], x, ln, ks, vs, kn, vn, B, L)  # (leaves the guide pass: GuideDone)
         lnarg = (stats, ln) if fold else None
         h = x if fold else self.layernorm(x, ln)
         no_lora = qs.lora is None and ks.lora is None and vs.lora is None
@@ -314,8 +322,14 @@ class BlockLowering(Lowering):
                     vt = self._project_vt(h, vs, B, L, C)
         if tap is not None and getattr(self, "sag_capture", True):
             self.sag_attention_mass(q, k, B, heads, L, C)
+        if ro is not None and ro[0] == "save":
+            self.reference_only_keep(ro[1], qk if qk is not None else k, k, vt, L, kn, vn)  # (pinned: the releases below leave them alone)
         if shared is not None:
             o = self.shared_attention(q, k, vt, qk, B, L, heads, shared)
+            if L % 64 == 0:
+                self.pool.put(vt)
+        elif ro is not None and ro[0] == "inject":
+            o = self.reference_only_attention(ro[1], ro[2], q, k, vt, B, heads, L, kn, vn)
             if L % 64 == 0:
                 self.pool.put(vt)
         elif native_path:
@@ -375,8 +389,16 @@ class BlockLowering(Lowering):
         heads = sd.num_heads
         src, Lk = ctx.tokens(pc[1].context, pc[1].key)
         in_step = (pc[1].context, pc[1].key) in getattr(self, "step_tokens", ())
-        with (self.in_step() if in_step else self.in_prologue()):
-            k, v_or_vt, v_plain = self.project_kv(src, B, kn, vn, heads)
+        # reference-only control: the guide copy's cross-attentions own the same Linears and read the same tokens, so the prologue projects them once
+        memo = None if in_step else getattr(self, "kv_memo", None)
+        mk = (pc[1].context, pc[1].key) + tuple(id(p) for n in (kn, vn) for p in n.parameters())
+        if memo is not None and mk in memo:
+            k, v_or_vt, v_plain = memo[mk]
+        else:
+            with (self.in_step() if in_step else self.in_prologue()):
+                k, v_or_vt, v_plain = self.project_kv(src, B, kn, vn, heads)
+            if memo is not None:
+                memo[mk] = (k, v_or_vt, v_plain)
         if adapted:
             self.stats["ella_sites"] = self.stats.get("ella_sites", 0) + 1
         streams = [(k, v_or_vt, Lk, 1.0)]
@@ -514,7 +536,7 @@ class BlockLowering(Lowering):
         """Run an unrecognised sub-tree through its own torch forward on an NCHW copy: the node-level half of the section 8(b) error convention
         ("unsupported => fall back to the stock child loop, never error", fluxion/layers/chain.py:226-243).  Only for sub-trees that do not touch
         the context store: at run time the Chain's contexts do not hold this program's tensors (residual slots, embeddings live in the lowered
-        program), so a node that reads or writes them -- FreeU's concatenator, reference-only attention injections -- makes the WHOLE
+        program), so a node that reads or writes them -- FreeU's concatenator -- makes the WHOLE
         tree fall back to the stock forward instead (Unsupported -> CompiledUNet.__call__).  The output geometry is whatever the node
         produces on a zero image of the input's shape (one trial call at lowering time)."""
         ctx_nodes = sorted({cname(s) for s in node.modules() if isa(s, "UseContext", "SetContext")})

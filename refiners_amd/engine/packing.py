@@ -170,6 +170,10 @@ class Pool:
     def pin(self, t: Tensor) -> None:
         self.pinned.add(t.data_ptr())
 
+    def unpin(self, t: Tensor) -> None:
+        """Inverse of pin: the buffer may go back to the free list with the next put."""
+        self.pinned.discard(t.data_ptr())
+
     def bytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.all)
 

@@ -15,6 +15,7 @@ from .. import native
 
 from .ella import EllaLowering
 from .lowering_blocks import BlockLowering
+from .reference_only import GuideDone, ReferenceOnlyLowering
 from .packing import Act, CatAct, ConvSpec, LinSpec, LoraPack, PackCache, Pool, Unsupported, _expect, cname, isa, kids, launches  # noqa: F401
 
 
@@ -82,11 +83,13 @@ class UNetIO:
     tokens: dict[tuple[str, str], tuple[Tensor, int]] = field(default_factory=dict)  # (context, key) -> ([B*Lp, width], L)
     conditions: dict[str, Tensor] = field(default_factory=dict)  # control context name -> [B, 3, 8H, 8W]
     t2i: dict[str, list[Tensor]] = field(default_factory=dict)  # T2I-Adapter name -> its feature maps, NCHW, batch 1 or B
+    guide: Optional[Tensor] = None  # reference-only control: the guide latents, a STEP input like x (noised per step by the caller)
 
 
-class UNetLowering(EllaLowering, BlockLowering):
+class UNetLowering(ReferenceOnlyLowering, EllaLowering, BlockLowering):
     """Lowers SDXLUNet / SD1UNet trees (reference xl/unet.py:258-351, sd1/unet.py:165-249), with ControlLoras at
-    index 0 (xl/control_lora.py:144-248) or an ELLA latents encoder there (latent_diffusion/ella_adapter.py:212-292, engine/ella.py), into `prologue` + `step`."""
+    index 0 (xl/control_lora.py:144-248), an ELLA latents encoder there (latent_diffusion/ella_adapter.py:212-292, engine/ella.py) or the guide pass of
+    reference-only control (latent_diffusion/reference_only_control.py:61-95, engine/reference_only.py), into `prologue` + `step`."""
 
     def lower(self, unet: Any, io: UNetIO) -> None:
         B, _, H, W = io.x.shape
@@ -96,36 +99,46 @@ class UNetLowering(EllaLowering, BlockLowering):
         n_slots = len(unet.init_context()["unet"]["residuals"])
         ctx.residuals = [None] * n_slots
         self.step_tokens = set()  # (context, key) of the token streams the step itself produces: their K / V^T projections are step work
-        cur: Any = None
+        self.reference_only_reset()
+        _expect(not any(isa(c, "SelfAttentionInjectionPassthrough") for c in kids(unet)[1:]), "SelfAttentionInjectionPassthrough is not the UNet's first child")
         with self.in_step():
-            for child in kids(unet):
-                if isa(child, "ControlLora"):
-                    self.control_lora(child, ctx, H, W)
-                elif isa(child, "Controlnet"):
-                    self.controlnet(child, ctx, H, W)
-                elif isa(child, "ELLA"):
-                    self.ella_child(child, ctx)
-                elif isa(child, "TimestepEncoder"):
-                    self.timestep_encoder(child, ctx, scope=unet)
-                elif cname(child) in ("DownBlocks", "UpBlocks"):
-                    for stage in kids(child):
-                        _expect(isa(stage, "Chain"), "UNet stages must be Chains")
-                        for piece in kids(stage):
-                            cur = self.piece(piece, cur, ctx, H, W)
-                elif cname(child) == "MiddleBlock":
-                    for piece in kids(child):
+            self.walk(unet, ctx, H, W)
+
+    def walk(self, unet: Any, ctx: UNetContext, H: int, W: int) -> None:
+        """The UNet's children in order (the step section is open); also the guide copy of reference-only control, which leaves it by GuideDone."""
+        cur: Any = None
+        for child in kids(unet):
+            if isa(child, "ControlLora"):
+                self.control_lora(child, ctx, H, W)
+            elif isa(child, "SelfAttentionInjectionPassthrough"):
+                self.reference_only_guide(child, unet, ctx, H, W)
+            elif isa(child, "TimestepEncoder") and self.reference_only_same_time(child):
+                pass  # (the guide pass has produced this embedding and the time biases: ctx shares them)
+            elif isa(child, "Controlnet"):
+                self.controlnet(child, ctx, H, W)
+            elif isa(child, "ELLA"):
+                self.ella_child(child, ctx)
+            elif isa(child, "TimestepEncoder"):
+                self.timestep_encoder(child, ctx, scope=unet)
+            elif cname(child) in ("DownBlocks", "UpBlocks"):
+                for stage in kids(child):
+                    _expect(isa(stage, "Chain"), "UNet stages must be Chains")
+                    for piece in kids(stage):
                         cur = self.piece(piece, cur, ctx, H, W)
-                elif isa(child, "Residual") and len(kids(child)) == 1 and self._reads_residuals(kids(child)[0]):
-                    cur = self.add_last_residual(cur, ctx)  # xl/unet.py:282
-                elif isa(child, "Sum") and len(kids(child)) == 2 and self._reads_residuals(kids(child)[0]) and cname(kids(child)[1]) == "MiddleBlock":
-                    for piece in kids(kids(child)[1]):  # sd1/unet.py:193-196: residuals[-1] + MiddleBlock(x)
-                        cur = self.piece(piece, cur, ctx, H, W)
-                    cur = self.add_last_residual(cur, ctx)
-                elif isa(child, "Chain") and [cname(k) for k in kids(child)] == ["GroupNorm", "SiLU", "Conv2d"]:
-                    cur = self.output_block(child, cur)
-                else:
-                    raise Unsupported(f"unexpected top-level UNet child {cname(child)}")
-            _expect(isinstance(cur, Tensor), "UNet did not end with an output block")
+            elif cname(child) == "MiddleBlock":
+                for piece in kids(child):
+                    cur = self.piece(piece, cur, ctx, H, W)
+            elif isa(child, "Residual") and len(kids(child)) == 1 and self._reads_residuals(kids(child)[0]):
+                cur = self.add_last_residual(cur, ctx)  # xl/unet.py:282
+            elif isa(child, "Sum") and len(kids(child)) == 2 and self._reads_residuals(kids(child)[0]) and cname(kids(child)[1]) == "MiddleBlock":
+                for piece in kids(kids(child)[1]):  # sd1/unet.py:193-196: residuals[-1] + MiddleBlock(x)
+                    cur = self.piece(piece, cur, ctx, H, W)
+                cur = self.add_last_residual(cur, ctx)
+            elif isa(child, "Chain") and [cname(k) for k in kids(child)] == ["GroupNorm", "SiLU", "Conv2d"]:
+                cur = self.output_block(child, cur)
+            else:
+                raise Unsupported(f"unexpected top-level UNet child {cname(child)}")
+        _expect(isinstance(cur, Tensor), "UNet did not end with an output block")
 
     @staticmethod
     def _reads_residuals(m: Any) -> bool:
@@ -342,7 +355,11 @@ class UNetLowering(EllaLowering, BlockLowering):
         if isa(m, "ResidualBlock"):
             out = self.residual_block(m, cur, ctx)
         elif isa(m, "CrossAttentionBlock2d"):
-            out = self.cross_attention_2d(m, cur, ctx)
+            try:
+                out = self.cross_attention_2d(m, cur, ctx)
+            except GuideDone:  # reference-only control: the guide copy ends inside this stage, its input goes back to the pool
+                self._release(cur)
+                raise
         elif isa(m, "Downsample"):
             ch = kids(m)
             conv = ch[-1]

@@ -1,1 +1,2 @@
 from .ella import ELLA, ELLAAdapter, SD1ELLAAdapter  # noqa: F401
+from .reference_only import ReferenceOnlyControlAdapter, SaveLayerNormAdapter, SelfAttentionInjectionAdapter, SelfAttentionInjectionPassthrough  # noqa: F401

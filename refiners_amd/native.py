@@ -78,6 +78,10 @@ LINEART_STRUCT_NAMES = {"mi355x_lineart_stem_args": "LineartStemArgs", "mi355x_l
                         "mi355x_lineart_in_apply_args": "LineartInApplyArgs", "mi355x_lineart_head_args": "LineartHeadArgs"}
 _abi_lineart = abi.read(LINEART_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_lineart.h")
 globals().update({cls.__name__: cls for cls in _abi_lineart.structs.values()})
+#: include/mi355x_refiners_reference_only.h, the joint self-attention of reference-only control
+REFERENCE_ONLY_STRUCT_NAMES = {"mi355x_attn_joint_args": "AttnJointArgs"}
+_abi_reference_only = abi.read(REFERENCE_ONLY_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_reference_only.h")
+globals().update({cls.__name__: cls for cls in _abi_reference_only.structs.values()})
 _K = _abi.constants
 
 #: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
@@ -96,6 +100,8 @@ EXPORTS_DINOV2 = list(_abi_dinov2.functions)
 EXPORTS_ELLA = list(_abi_ella.functions)
 #: every symbol include/mi355x_refiners_lineart.h declares
 EXPORTS_LINEART = list(_abi_lineart.functions)
+#: every symbol include/mi355x_refiners_reference_only.h declares
+EXPORTS_REFERENCE_ONLY = list(_abi_reference_only.functions)
 #: exported for probing and A/B runs, by design not in the header (no stable contract): name -> (restype, argtypes), applied by load() like the header's
 UNSTABLE = {
     "mi355x_set_option": (C.c_int, [C.c_char_p, C.c_int]),
@@ -191,7 +197,7 @@ def load(path: Optional[Path] = None) -> C.CDLL:
         lib = C.CDLL(str(p))
     except OSError as e:  # e.g. no HIP runtime on this machine
         raise NativeError(f"cannot load {p}: {e}") from e
-    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **_abi_mvanet.functions, **_abi_dinov2.functions, **_abi_ella.functions, **_abi_lineart.functions, **UNSTABLE}.items():
+    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **_abi_mvanet.functions, **_abi_dinov2.functions, **_abi_ella.functions, **_abi_lineart.functions, **_abi_reference_only.functions, **UNSTABLE}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.mi355x_abi_version() != ABI_VERSION:
@@ -877,6 +883,32 @@ def attention_general(
     a.scale = scale if scale is not None else a.Dqk ** -0.5
     a.out_scale = out_scale
     _launch("mi355x_attention_general", (C.byref(a),), "mi355x_attention_general")
+    return out
+
+
+def attention_joint(q: Tensor, k0: Tensor, vt0: Tensor, Lk0: int, k1: Tensor, vt1: Tensor, Lk1: int, out: Tensor, num_heads: int,
+                    mix: Optional[Tensor] = None, scale: Optional[float] = None) -> Tensor:
+    """mi355x_attention_joint (csrc/reference_only.hip): out[b] = mix[b] * SDPA(q, [k0 ; k1], [v0 ; v1]) + (1 - mix[b]) * SDPA(q, k0, v0).
+    q, out [B, Lq, H*D]; k0 / k1 [B, Lk(+), H*D] (column slices of a wider buffer are fine); vt0 / vt1 [H*D, B, Lkp] with Lkp the segment's Lk
+    rounded up to 64 and finite padding -- views with a contiguous last dimension.  mix: float32 [B] on the device, or None (all ones)."""
+    a = AttnJointArgs()
+    B, Lq, HD = q.shape
+    assert HD % num_heads == 0 and vt0.shape[0] == HD and vt1.shape[0] == HD and out.shape[2] == HD
+    assert all(t.stride(2) == 1 for t in (q, k0, vt0, k1, vt1, out)) and all(t.dtype == q.dtype for t in (k0, vt0, k1, vt1, out))
+    assert vt0.shape[2] >= -(-Lk0 // 64) * 64 and vt1.shape[2] >= -(-Lk1 // 64) * 64 and k0.shape[1] >= Lk0 and k1.shape[1] >= Lk1
+    a.dtype = dtype_code(q.dtype)
+    a.B, a.H, a.Lq, a.D, a.Lk0, a.Lk1 = B, num_heads, Lq, HD // num_heads, Lk0, Lk1
+    a.q, a.ldq, a.q_batch_stride = q.data_ptr(), q.stride(1), q.stride(0)
+    a.k0, a.ldk0, a.k0_batch_stride = k0.data_ptr(), k0.stride(1), k0.stride(0)
+    a.vt0, a.ldvt0, a.vt0_batch_stride = vt0.data_ptr(), vt0.stride(0), vt0.stride(1)
+    a.k1, a.ldk1, a.k1_batch_stride = k1.data_ptr(), k1.stride(1), k1.stride(0)
+    a.vt1, a.ldvt1, a.vt1_batch_stride = vt1.data_ptr(), vt1.stride(0), vt1.stride(1)
+    if mix is not None:
+        assert mix.dtype == torch.float32 and tuple(mix.shape) == (B,) and mix.is_contiguous() and mix.device == q.device
+        a.mix = mix.data_ptr()
+    a.out, a.ldo, a.o_batch_stride = out.data_ptr(), out.stride(1), out.stride(0)
+    a.scale = scale if scale is not None else a.D ** -0.5
+    _launch("mi355x_attention_joint", (C.byref(a),), "mi355x_attention_joint", keep=(q, k0, vt0, k1, vt1, mix, out))
     return out
 
 
