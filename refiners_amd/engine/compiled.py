@@ -436,6 +436,10 @@ class CompiledSDXL:
         self.graph_key: Any = None
         self.inputs: dict[str, Any] = {}
         self.engine2: Optional[CompiledUNet] = None  # self-attention guidance: the second (unconditional, batch n) UNet pass
+        # step-constant UNet input channels (inpainting: mask + masked-image latents, IC-Light: the condition latents): an engine-owned buffer at a
+        # stable address, [1 or n, E, h, w]; the UNet then reads (2n or n, 4 + E, h, w) and x stays (n, 4, h, w)
+        self.cond: Optional[Tensor] = None
+        self.in_scale: Optional[Tensor] = None  # one float32 on the device: the solver's input scale of the step that primes the model input
 
     @property
     def condition_scale(self) -> float:
@@ -478,6 +482,10 @@ class CompiledSDXL:
                 rows.append([self.condition_scale, cur, sig, prev, nf, 0.0, 0.0, 0.0])
         self.coef_table = torch.tensor(rows, dtype=torch.float32, device=device)
         self.coef = torch.zeros(8, dtype=torch.float32, device=device)
+        # a solver whose input scale is 1 at every step (DDIM, DPM-Solver++, LCM) leaves the constant input channels as priming wrote them; Euler's
+        # are rescaled by every step's last launch (mi355x_cond_step with the constants given)
+        self.scales_input = self.linear and any(float(self.solver.input_scale(s)) != 1.0 for s in range(self.solver.num_inference_steps))
+        self.in_scale = torch.ones(1, dtype=torch.float32, device=device)
         self.ts_table = self.solver.timesteps.to(device=device, dtype=torch.float32)
         # Self-Attention Guidance degrades the latents through Solver.remove_noise / add_noise: (-, scale_t, std_t) per step, for mi355x_sag_degrade.
         # A solver whose add_noise / remove_noise the reference itself cannot evaluate (Euler: float timesteps) has no table; SAG then raises.
@@ -496,12 +504,17 @@ class CompiledSDXL:
 
     def set_inputs(self, x: Tensor, *, clip_text_embedding: Tensor, pooled_text_embedding: Optional[Tensor] = None, time_ids: Optional[Tensor] = None,
                    clip_image_embedding: Optional[Tensor] = None, conditions: Optional[dict[str, Tensor]] = None,
-                   t2i_features: Optional[dict[str, Any]] = None, generator: Optional[torch.Generator] = None, llm_text_embedding: Optional[Tensor] = None) -> None:
+                   t2i_features: Optional[dict[str, Any]] = None, generator: Optional[torch.Generator] = None, llm_text_embedding: Optional[Tensor] = None,
+                   input_condition: Optional[Tensor] = None) -> None:
         """x: (N, 4, H, W) initial latents; embeddings are [negative ; conditional] stacks of 2N rows;
         `conditions` maps a ControlLora name to its control image, (2N, 3, 8H, 8W) or ONE picture (1, 3, 8H, 8W) for the whole batch; `t2i_features` maps a T2I-Adapter name to
         the tuple its `compute_condition_features` returned (batch 1 or 2N); `llm_text_embedding` (2N, T, width): the LLM's token embeddings an injected ELLA adapter reads
         (ELLAAdapter.set_llm_text_embedding).
-        With `classifier_free_guidance=False` there is no negative half: embeddings have N rows, pictures and features 1 or N."""
+        With `classifier_free_guidance=False` there is no negative half: embeddings have N rows, pictures and features 1 or N.
+        `input_condition` (1 or N, E, H, W): the channels the UNet reads BEHIND the latents and that do not change over a trajectory -- inpainting's
+        cat(mask_latents, target_image_latents), IC-Light's condition latents.  x stays (N, 4, H, W); the UNet's first convolution must read 4 + E
+        channels.  New values of the same shape keep the lowered program and the captured graph (the model input is primed again); another shape
+        or leaving it out drops the graph."""
         if not self._cfg:
             n = x.shape[0]
             for what, t in (("clip_text_embedding", clip_text_embedding), ("pooled_text_embedding", pooled_text_embedding), ("time_ids", time_ids),
@@ -517,7 +530,8 @@ class CompiledSDXL:
         if llm_text_embedding is not None:
             tokens[("adapted_cross_attention_block", "llm_text_embedding")] = llm_text_embedding
         self.inputs = {"pooled": pooled_text_embedding, "time_ids": time_ids, "tokens": tokens,
-                       "conditions": {f"control_lora_{k}": v for k, v in (conditions or {}).items()},
+                       # ("controlnet.condition_<name>": the picture of an SD1.5 Controlnet, under the context and key its adapter reads)
+                       "conditions": {(k if k.startswith("controlnet.") else f"control_lora_{k}"): v for k, v in (conditions or {}).items()},
                        "t2i": {k: tuple(v) for k, v in (t2i_features or {}).items()}}
         if self.x is None or self.x.shape != x.shape or self.x.device != x.device or self.x.dtype != self.unet.dtype:
             self.x = torch.empty(tuple(x.shape), device=x.device, dtype=self.unet.dtype)
@@ -526,10 +540,20 @@ class CompiledSDXL:
             self.hist = torch.zeros_like(self.x)
             self.graph = None
         self.x.copy_(x)
-        if self.linear or not self._cfg:
+        if input_condition is None:
+            if self.cond is not None:
+                self.cond, self.graph = None, None
+        else:
+            assert input_condition.dim() == 4 and input_condition.shape[0] in (1, x.shape[0]) and tuple(input_condition.shape[2:]) == tuple(x.shape[2:]), (
+                f"input_condition is {tuple(input_condition.shape)}: expected (1 or {x.shape[0]}, E, {x.shape[2]}, {x.shape[3]}) beside latents {tuple(x.shape)}")
+            if self.cond is None or self.cond.shape != input_condition.shape or self.cond.device != x.device or self.cond.dtype != self.unet.dtype:
+                self.cond = torch.empty(tuple(input_condition.shape), device=x.device, dtype=self.unet.dtype)
+                self.graph = None  # the captured launches hold the buffer's address
+            self.cond.copy_(input_condition)
+        if self.linear or not self._cfg or self.cond is not None:
             assert self.hist is not None
             self.hist.zero_()
-            self.primed = False  # the model-input buffer must be (re)filled with s_0 * x before the next step
+            self.primed = False  # the model-input buffer must be (re)filled with s_0 * x (and s_0 * the constant channels) before the next step
         if self.coef_table is None or self.coef_table.device != x.device:
             self._tables(x.device)
 
@@ -541,8 +565,8 @@ class CompiledSDXL:
     SPLIT_MAX_IMAGES = 0
 
     def _split_wanted(self, n: int) -> bool:
-        if not self._cfg or self._sag_adapter() is not None or self.x is None or self.x.device.type != "cuda":
-            return False
+        if not self._cfg or self._sag_adapter() is not None or self.x is None or self.x.device.type != "cuda" or self.cond is not None:
+            return False  # (step-constant input channels keep the single program, as Self-Attention Guidance does)
         if self.cfg_split is None and self.engine.reference_only():
             return False  # reference-only control blends row 0 of the pair with the guide's keys: one program (an explicit cfg_split=True is refused by the lowering)
         return self.cfg_split if self.cfg_split is not None else n <= self.SPLIT_MAX_IMAGES
@@ -661,21 +685,46 @@ class CompiledSDXL:
             self.engine_c.prologue_key = None  # type: ignore[union-attr]
             return
         try:
-            self.engine.prepare_explicit(((2 * n if self._cfg else n),) + tuple(self.x.shape[1:]), self.x.device, dict(self.inputs, timestep=self.ts_table[0:1], timesteps_all=self.ts_table, step_index=0))
+            self.engine.prepare_explicit(self._model_shape(n), self.x.device, dict(self.inputs, timestep=self.ts_table[0:1], timesteps_all=self.ts_table, step_index=0))
         except Unsupported:
             return  # a tree this lowering does not know: nothing to stage, step() takes the stock Chain forward with its warning (the fallback contract)
         self.engine.prologue_key = None  # staged, not yet run: the first step() re-stages and runs the prologue
 
+    def _model_shape(self, n: int, rows: Optional[int] = None) -> tuple:
+        """The UNet's input: the CFG pair (or x alone) with the step-constant channels behind the latents'."""
+        x = self.x
+        assert x is not None
+        E = 0 if self.cond is None else self.cond.shape[1]
+        return (rows if rows is not None else (2 * n if self._cfg else n), x.shape[1] + E) + tuple(x.shape[2:])
+
+    def _check_stem(self) -> None:
+        """The UNet's first convolution must read the latents' channels plus the condition's."""
+        from .packing import cname
+
+        x = self.x
+        assert x is not None
+        down = next((m for m in kids(self.engine._tree()) if cname(m) == "DownBlocks"), None)
+        conv = None if down is None else next((m for m in down.modules() if isa(m, "Conv2d")), None)
+        if conv is not None and self.cond is not None:
+            E = self.cond.shape[1]
+            assert conv.in_channels == x.shape[1] + E, (
+                f"the UNet's first convolution reads {conv.in_channels} channels, the latents have {x.shape[1]} and input_condition {E}: {x.shape[1]} + {E} != {conv.in_channels}")
+
     def _fill(self, io: Any = None) -> None:
         io = io if io is not None else self.engine.io
         n = self.x.shape[0]  # type: ignore[union-attr]
+        if self.cond is not None:  # latents and constants into both halves, scaled by the priming step's input scale (set by the caller)
+            native.cond_fill(self.x, self.cond, io.x, self.in_scale, n, self.x.shape[1])  # type: ignore[union-attr]
+            return
         io.x[:n].copy_(self.x)  # type: ignore[union-attr]
         if self._cfg:
             io.x[n:].copy_(self.x)  # type: ignore[union-attr]
 
     def _update(self, io: Any) -> None:
         """The step's last launch: (guidance +) solver update + history + the next step's model input."""
-        if self._cfg:
+        if self.cond is not None:
+            native.cond_step(self.x, io.out, self.hist, io.x, self.cond if self.scales_input else None, self.coef, self.linear, self._cfg)
+        elif self._cfg:
             native.cfg_linear_step(self.x, io.out, self.hist, io.x, self.coef)
         elif self.linear:
             native.linear_step(self.x, io.out, self.hist, io.x, self.coef)
@@ -699,7 +748,8 @@ class CompiledSDXL:
             return self._split_step(step, got, n)
         eng.io_override = None
         eng.sag_capture = self._cfg  # (no guidance, no Self-Attention Guidance: the tap's column mass would be computed and never read)
-        shape2 = ((2 * n if self._cfg else n),) + tuple(self.x.shape[1:])
+        shape2 = self._model_shape(n)
+        self._check_stem()
         try:
             changed = eng.prepare_explicit(shape2, self.x.device, got)
         except Unsupported:
@@ -711,13 +761,13 @@ class CompiledSDXL:
         assert io is not None and low is not None
         self.coef.copy_(self.coef_table[step])
         if not self._cfg:  # the UNet program on x alone, then mi355x_linear_step / mi355x_ddim_step (DDIM too keeps its model input primed: no copy per step)
-            return self._linear_step(step, io, low, eng, None, ("free", eng.key))
+            return self._linear_step(step, io, low, eng, None, ("free", eng.key) + self._cond_id())
         sag = self._sag_adapter()
         tail = None if sag is None else self._prepare_sag(sag, got, n, io, low, step)
         # everything a captured graph holds by value or by address: both programs, and for self-attention guidance the host-side ratio
         # sag.scale / condition_scale and the blur weights' tensor (kernel_size, sigma)
-        gkey = (eng.key, None if self.engine2 is None or sag is None else (self.engine2.key, float(sag.scale) / float(self.condition_scale), int(sag.kernel_size), float(sag.sigma)))
-        if self.linear:
+        gkey = (eng.key, None if self.engine2 is None or sag is None else (self.engine2.key, float(sag.scale) / float(self.condition_scale), int(sag.kernel_size), float(sag.sigma))) + self._cond_id()
+        if self.linear or self.cond is not None:  # (with step-constant channels DDIM too keeps its model input primed: mi355x_cond_step writes the next one)
             return self._linear_step(step, io, low, eng, tail, gkey)
         if tail is None:
             tail = lambda: None  # noqa: E731
@@ -744,6 +794,10 @@ class CompiledSDXL:
         self.graph.replay()
         return self.x
 
+    def _cond_id(self) -> tuple:
+        """What a captured graph holds of the step-constant channels: the buffer's address and shape, and whether the last launch rescales them."""
+        return () if self.cond is None else ((self.cond.data_ptr(), tuple(self.cond.shape), self.scales_input),)
+
     # -- whole-tree fallback ------------------------------------------------------------------------------------------------------
     def _stock_step(self, step: int, got: dict[str, Any]) -> Tensor:
         """A tree the lowering refused (CompiledUNet.prepare_explicit warned and recorded why): the step runs like the reference's
@@ -764,7 +818,9 @@ class CompiledSDXL:
         for name, feats in got.get("t2i", {}).items():
             unet.set_context("t2iadapter", {f"condition_features_{name}": tuple(f.to(x.dtype) for f in feats)})
         self.coef.copy_(self.coef_table[step])
-        xin = torch.cat((x, x)) if self._cfg else x
+        # the extended input, as StableDiffusion_1_Inpainting.forward / ICLight build it: cat along the channels in front of the CFG pair
+        xm = x if self.cond is None else torch.cat((x, self.cond.expand(x.shape[0], -1, -1, -1)), dim=1)
+        xin = torch.cat((xm, xm)) if self._cfg else xm
         if not self.linear:
             if self._cfg:
                 native.cfg_ddim_step(x, unet(xin).contiguous(), self.coef)
@@ -821,7 +877,7 @@ class CompiledSDXL:
         got2 = {"timestep": got["timestep"], "timesteps_all": got.get("timesteps_all"), "step_index": got.get("step_index", 0), **halves[1],
                 "conditions": got["conditions"], "t2i": got.get("t2i", {})}
         x = self.x
-        if e2.prepare_explicit((n,) + tuple(x.shape[1:]), x.device, got2):
+        if e2.prepare_explicit(self._model_shape(n, rows=n), x.device, got2):
             e2.run_prologue()
         io2, low2 = e2.io, e2.low
         ks, sigma = int(sag.kernel_size), float(sag.sigma)
@@ -834,10 +890,16 @@ class CompiledSDXL:
         assert ah * aw == low.sag["tokens"]
         ratio = float(sag.scale) / float(self.condition_scale)
         u, c = io.out[:n], io.out[n:]
+        cond = self.cond
+        if cond is not None and (getattr(self, "_sag_deg", None) is None or self._sag_deg.shape != x.shape or self._sag_deg.dtype != x.dtype or self._sag_deg.device != x.device):
+            self._sag_deg = torch.empty_like(x)  # mi355x_sag_degrade writes contiguous latents; mi355x_cond_fill re-strides them in front of the constants
+        deg = self._sag_deg if cond is not None else io2.x
 
         def tail() -> None:
             # x is the UNSCALED latent (model.py:146: the guidance sees x, not scale_model_input(x)), and so is what the second pass is fed
-            native.sag_degrade(x, u, mass, (ah, aw), self.sag_coef, self._sag_w1, io2.x)
+            native.sag_degrade(x, u, mass, (ah, aw), self.sag_coef, self._sag_w1, deg)
+            if cond is not None:  # cat(degraded, constants), unscaled (stable_diffusion_1/model.py:288-333)
+                native.cond_fill(deg, cond, io2.x, None, n, x.shape[1])
             native.replay(low2.step)
             native.axpby(u, ratio, c, 1.0, c)
             native.axpby(io2.out, -ratio, c, 1.0, c)
@@ -863,9 +925,11 @@ class CompiledSDXL:
             noise = torch.randn(tuple(self.x.shape), generator=getattr(self, "generator", None), device=sdev, dtype=sdt)
             self.hist.copy_(noise)
         if not self.primed or self.primed_key != gkey:  # first step of a trajectory, or the engine re-lowered into new buffers
-            self._fill(io)  # cat(x, x) (x alone without guidance) ...
             s0 = float(self.solver.input_scale(step)) if self.linear else 1.0  # (DDIM does not scale its model input)
-            if s0 != 1.0:
+            if self.cond is not None:
+                self.in_scale.fill_(s0)  # type: ignore[union-attr]  # mi355x_cond_fill reads it from the device
+            self._fill(io)  # cat(x, x) (x alone without guidance) ...
+            if s0 != 1.0 and self.cond is None:
                 io.x.mul_(s0)  # ... through Solver.scale_model_input for THIS step; later steps get it from the kernel
             self.primed, self.primed_key = True, gkey
         if not self.use_graph:

@@ -323,15 +323,22 @@ class UNetLowering(ReferenceOnlyLowering, EllaLowering, BlockLowering):
         """First convolution, straight from the NCHW latents (im2col of the tiny-channel image, then one GEMM)."""
         _expect(isa(conv, "Conv2d") and conv.kernel_size == (3, 3) and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (1, 1), "unsupported stem conv")
         B, cin, H, W = self.io.x.shape
-        _expect(conv.in_channels == cin, "stem conv channel mismatch")
+        cw = conv.in_channels
+        # a Controlnet in front of a UNet with step-constant input channels (inpainting: 9) reads Slicing(:4) of the UNet's input: its stem weight is
+        # packed with zeros in the other channels' columns, so that it multiplies the SAME im2col layout as the UNet's own stem (no slicing kernel)
+        sliced = getattr(self, "stem_first_channels", None)
+        _expect(cw == cin or (sliced is not None and cw == sliced and cw < cin), f"stem conv channel mismatch (the conv reads {cw} channels, the model input has {cin})")
         kp = (9 * cin + self.kblk - 1) // self.kblk * self.kblk
 
         def pack() -> Tensor:
             wp = torch.zeros(conv.out_channels, kp, device=self.device, dtype=self.dtype)
-            wp[:, : 9 * cin] = native.pack_conv_weight(self.cvt(conv.weight))
+            if cw == cin:
+                wp[:, : 9 * cin] = native.pack_conv_weight(self.cvt(conv.weight))
+            else:  # K is ordered (ky, kx, channel): the conv's channels are the first cw of every tap
+                wp[:, : 9 * cin].view(conv.out_channels, 9, cin)[:, :, :cw] = native.pack_conv_weight(self.cvt(conv.weight)).view(conv.out_channels, 9, cw)
             return wp
 
-        wp = self.cache.get(("stem", kp) + PackCache.ident(conv.weight), pack)
+        wp = self.cache.get((("stem", kp) if cw == cin else ("stem_first", kp, cin)) + PackCache.ident(conv.weight), pack)
         cols = self.pool.get(B * H * W, kp)
         native.im2col3x3_nchw(self.io.x, cols)
         out = self.pool.get(B * H * W, conv.out_channels)
@@ -547,18 +554,22 @@ class UNetLowering(ReferenceOnlyLowering, EllaLowering, BlockLowering):
         ch = kids(node)
         _expect(len(ch) == 4 and isa(ch[0], "TimestepEncoder") and isa(ch[1], "Slicing") and cname(ch[2]) == "DownBlocks" and cname(ch[3]) == "MiddleBlock",
                 "unexpected Controlnet layout")
-        _expect(ch[1].dim == 1 and ch[1].start == 0 and ch[1].end == 4 and self.io.x.shape[1] == 4, "Controlnet on a UNet input with more than 4 channels is not lowered")
+        _expect(ch[1].dim == 1 and ch[1].start == 0 and ch[1].end == 4 and self.io.x.shape[1] >= 4, "unexpected Controlnet input slice")
         sub = UNetContext(self, ctx.B, text=ctx.text, temb_silu=ctx.temb_silu, residuals=ctx.residuals, shapes=[])
         self.timestep_encoder(ch[0], sub, scope=node)
         cur: Optional[Act] = None
         stages = [(n, kids(stage)) for n, stage in enumerate(kids(ch[2]))] + [(12, kids(ch[3]))]
         _expect(len(stages) == 13, "Controlnet must have 12 down blocks and a middle block")
-        for n, pieces in stages:
-            for piece in pieces:
-                if isa(piece, "Passthrough") and len(kids(piece)) == 2 and isa(kids(piece)[0], "Conv2d") and isa(kids(piece)[1], "Lambda"):
-                    self.controlnet_tap(node, kids(piece)[0], n, cur, sub)
-                else:
-                    cur = self.piece(piece, cur, sub, H, W)
+        self.stem_first_channels = 4  # Slicing(:4) of a wider UNet input: see stem()
+        try:
+            for n, pieces in stages:
+                for piece in pieces:
+                    if isa(piece, "Passthrough") and len(kids(piece)) == 2 and isa(kids(piece)[0], "Conv2d") and isa(kids(piece)[1], "Lambda"):
+                        self.controlnet_tap(node, kids(piece)[0], n, cur, sub)
+                    else:
+                        cur = self.piece(piece, cur, sub, H, W)
+        finally:
+            self.stem_first_channels = None
         self._release(cur)
         self.stats["controlnets"] = self.stats.get("controlnets", 0) + 1
 

@@ -200,22 +200,32 @@ class CompiledVAEEncoder:
         self.stats: dict[str, Any] = {}
 
     @torch.no_grad()
-    def __call__(self, image: Tensor) -> Tensor:
+    def prepare(self, shape: tuple, device: torch.device) -> Tensor:
+        """Lower for an image of `shape` and return the program's input buffer `self.x`: a producer that runs on the device (the inpainting
+        conditions' kernel) writes the image there and calls `run()`, with no copy in between."""
         from ..fluxion.tree import tree_epoch
 
         enc = kids(self.vae)[0]
         dtype = enc.dtype
-        key = (tree_epoch(), tuple(image.shape), dtype, image.device, float(self.vae.encoder_scale))
+        key = (tree_epoch(), tuple(shape), dtype, device, float(self.vae.encoder_scale))
         if key != self.key:
-            B, _, H, W = image.shape
+            B, _, H, W = shape
             assert H % 8 == 0 and W % 8 == 0, "the autoencoder downsamples by 8"
-            self.x = torch.empty(tuple(image.shape), device=image.device, dtype=dtype)
-            self.out = torch.empty(B, 4, H // 8, W // 8, device=image.device, dtype=dtype)
-            low = VAEDecoderLowering(image.device, dtype, self.cache)
+            self.x = torch.empty(tuple(shape), device=device, dtype=dtype)
+            self.out = torch.empty(B, 4, H // 8, W // 8, device=device, dtype=dtype)
+            low = VAEDecoderLowering(device, dtype, self.cache)
             low.lower_encoder(enc, self.x, self.out, float(self.vae.encoder_scale))
             self.cache.sweep()
             self.low, self.key = low, key
             self.stats = dict(low.stats, step_ops=launches(low.step), pool_bytes=low.step_pool.bytes())
-        self.x.copy_(image)
+        return self.x
+
+    @torch.no_grad()
+    def run(self) -> Tensor:
         native.replay(self.low.step)
         return self.out.clone()
+
+    @torch.no_grad()
+    def __call__(self, image: Tensor) -> Tensor:
+        self.prepare(tuple(image.shape), image.device).copy_(image)
+        return self.run()

@@ -82,6 +82,8 @@ globals().update({cls.__name__: cls for cls in _abi_lineart.structs.values()})
 REFERENCE_ONLY_STRUCT_NAMES = {"mi355x_attn_joint_args": "AttnJointArgs"}
 _abi_reference_only = abi.read(REFERENCE_ONLY_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_reference_only.h")
 globals().update({cls.__name__: cls for cls in _abi_reference_only.structs.values()})
+#: include/mi355x_refiners_cond_input.h, step-constant UNet input channels (inpainting, IC-Light; no structs)
+_abi_cond_input = abi.read({}, abi.HEADER.parent / "mi355x_refiners_cond_input.h")
 _K = _abi.constants
 
 #: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
@@ -102,6 +104,8 @@ EXPORTS_ELLA = list(_abi_ella.functions)
 EXPORTS_LINEART = list(_abi_lineart.functions)
 #: every symbol include/mi355x_refiners_reference_only.h declares
 EXPORTS_REFERENCE_ONLY = list(_abi_reference_only.functions)
+#: every symbol include/mi355x_refiners_cond_input.h declares
+EXPORTS_COND_INPUT = list(_abi_cond_input.functions)
 #: exported for probing and A/B runs, by design not in the header (no stable contract): name -> (restype, argtypes), applied by load() like the header's
 UNSTABLE = {
     "mi355x_set_option": (C.c_int, [C.c_char_p, C.c_int]),
@@ -197,7 +201,7 @@ def load(path: Optional[Path] = None) -> C.CDLL:
         lib = C.CDLL(str(p))
     except OSError as e:  # e.g. no HIP runtime on this machine
         raise NativeError(f"cannot load {p}: {e}") from e
-    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **_abi_mvanet.functions, **_abi_dinov2.functions, **_abi_ella.functions, **_abi_lineart.functions, **_abi_reference_only.functions, **UNSTABLE}.items():
+    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **_abi_mvanet.functions, **_abi_dinov2.functions, **_abi_ella.functions, **_abi_lineart.functions, **_abi_reference_only.functions, **_abi_cond_input.functions, **UNSTABLE}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.mi355x_abi_version() != ABI_VERSION:
@@ -1070,6 +1074,57 @@ def linear_step(x: Tensor, unet_out: Tensor, hist: Tensor, model_in: Optional[Te
     _launch("mi355x_linear_step", (dtype_code(x.dtype), x.data_ptr(), unet_out.data_ptr(), hist.data_ptr(), model_in.data_ptr() if model_in is not None else None,
                                   coef.data_ptr(), x.numel()), "mi355x_linear_step")
     return x
+
+
+def _cond_geometry(x_like: tuple, model_in: Tensor, cond: Optional[Tensor]) -> tuple[int, int, int, int, int]:
+    """(n, C, E, nc, hw) of latents [n, C, h, w], a model input [n or 2n, C + E, h, w] and constants [1 or n, E, h, w] (or None)."""
+    n, Cc, h, w = x_like
+    assert model_in.dim() == 4 and model_in.is_contiguous() and tuple(model_in.shape[2:]) == (h, w) and model_in.shape[1] >= Cc
+    E = model_in.shape[1] - Cc
+    nc = 1
+    if cond is not None:
+        assert cond.is_contiguous() and cond.dtype == model_in.dtype and tuple(cond.shape[1:]) == (E, h, w) and cond.shape[0] in (1, n), (tuple(cond.shape), (n, E, h, w))
+        nc = cond.shape[0]
+    return n, Cc, E, nc, h * w
+
+
+def cond_step(x: Tensor, unet_out: Tensor, hist: Optional[Tensor], model_in: Tensor, cond: Optional[Tensor], coef: Tensor, linear: bool, guided: bool) -> Tensor:
+    """The step's last launch of a UNet with step-constant input channels (see mi355x_cond_step in its header): x, hist [n, C, h, w] in place;
+    unet_out [2n or n, C, h, w]; model_in [2n or n, C + E, h, w]; cond [1 or n, E, h, w], or None to leave the constant channels as they are."""
+    n, Cc, E, nc, hw = _cond_geometry(tuple(x.shape), model_in, cond)
+    B = 2 * n if guided else n
+    assert x.is_contiguous() and unet_out.is_contiguous() and tuple(unet_out.shape) == (B,) + tuple(x.shape[1:]) and model_in.shape[0] == B
+    assert unet_out.dtype == x.dtype == model_in.dtype and coef.dtype == torch.float32 and coef.numel() >= 8
+    assert not linear or (hist is not None and hist.is_contiguous() and hist.shape == x.shape and hist.dtype == x.dtype)
+    _launch("mi355x_cond_step", (dtype_code(x.dtype), _abi_cond_input.constants["MI355X_COND_LINEAR" if linear else "MI355X_COND_DDIM"], int(guided), x.data_ptr(),
+                                unet_out.data_ptr(), hist.data_ptr() if (linear and hist is not None) else None, model_in.data_ptr(),
+                                cond.data_ptr() if cond is not None else None, coef.data_ptr(), n, Cc, E, nc, hw), "mi355x_cond_step", keep=(cond,))
+    return x
+
+
+def cond_fill(x: Optional[Tensor], cond: Optional[Tensor], model_in: Tensor, s: Optional[Tensor], n: int, channels: int) -> Tensor:
+    """model_in[b, :channels] = s x[b % n] (x given) and model_in[b, channels:] = s cond[0 or b % n] (cond given) for every row b of model_in
+    [n or 2n, channels + E, h, w]; s: one float32 on the device, None = 1 (see mi355x_cond_fill in its header)."""
+    h, w = model_in.shape[2:]
+    n, Cc, E, nc, hw = _cond_geometry((n, channels, h, w), model_in, cond)
+    assert x is None or (x.is_contiguous() and tuple(x.shape) == (n, Cc, h, w) and x.dtype == model_in.dtype)
+    assert s is None or (s.dtype == torch.float32 and s.numel() >= 1 and s.is_cuda)
+    _launch("mi355x_cond_fill", (dtype_code(model_in.dtype), x.data_ptr() if x is not None else None, cond.data_ptr() if cond is not None else None, model_in.data_ptr(),
+                                s.data_ptr() if s is not None else None, n, model_in.shape[0], Cc, E, nc, hw), "mi355x_cond_fill", keep=(x, cond, s))
+    return model_in
+
+
+def inpaint_conditions(image: Tensor, mask: Tensor, masked_image: Tensor, mask_latents: Tensor) -> tuple[Tensor, Tensor]:
+    """image uint8 [n, H, W, 3], mask uint8 [1 or n, H, W] -> masked_image [n, 3, H, W] and mask_latents [1 or n, 1, h, w] in the model dtype
+    (see mi355x_inpaint_conditions in its header)."""
+    n, H, W, three = image.shape
+    nm = mask.shape[0]
+    assert three == 3 and image.dtype == torch.uint8 and mask.dtype == torch.uint8 and image.is_contiguous() and mask.is_contiguous()
+    assert tuple(mask.shape) == (nm, H, W) and nm in (1, n) and tuple(masked_image.shape) == (n, 3, H, W) and masked_image.is_contiguous()
+    assert mask_latents.dim() == 4 and tuple(mask_latents.shape[:2]) == (nm, 1) and mask_latents.is_contiguous() and mask_latents.dtype == masked_image.dtype
+    _launch("mi355x_inpaint_conditions", (dtype_code(masked_image.dtype), image.data_ptr(), mask.data_ptr(), masked_image.data_ptr(), mask_latents.data_ptr(), n, nm, H, W,
+                                         mask_latents.shape[2], mask_latents.shape[3]), "mi355x_inpaint_conditions", keep=(image, mask))
+    return masked_image, mask_latents
 
 
 def sinusoidal(x: Tensor, dim: int, out: Tensor, group: int = 1, col0: int = 0) -> Tensor:
