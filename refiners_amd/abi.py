@@ -23,7 +23,7 @@ _STATEMENT = re.compile(
     r"|typedef\s+struct\s*\w*\s*\{(?P<fields>[^{}]*)\}\s*(?P<struct>\w+)\s*;"
     r"|(?P<ret>\w+)\s+(?P<func>\w+)\s*\((?P<params>[^()]*)\)\s*;"
 )
-_PREPROCESSOR = re.compile(rf"#\s*(?:define\s+(?P<name>\w+)\s+(?P<value>{_INT})|define\s+\w+|ifndef\s+\w+|endif|include\s*<\w+\.h>)\s*")
+_PREPROCESSOR = re.compile(rf'#\s*(?:define\s+(?P<name>\w+)\s+(?P<value>{_INT})|define\s+\w+|ifndef\s+\w+|endif|include\s*<\w+\.h>|include\s*"mi355x_refiners\.h")\s*')
 _FIELD = re.compile(r"(?P<const>const\s+)?(?P<type>\w+)(?:\s*(?P<ptr>\*)\s*|\s+)(?P<names>[^*\s].*)", re.S)
 _DECLARATOR = re.compile(r"(?P<name>[A-Za-z_]\w*)\s*(?:\[\s*(?P<dim>\w+)\s*\])?")
 _SPACE = re.compile(r"\s*")
@@ -45,11 +45,15 @@ def _blank(m: re.Match) -> str:
     return " " + "\n" * m.group().count("\n")  # the text keeps its lines, so a position still names the header line
 
 
-def parse(text: str, names: dict, where: str = "header") -> Abi:
-    """`names`: C struct name -> name of the Python class; a struct the header declares and `names` lacks is an error."""
+def parse(text: str, names: dict, where: str = "header", base: Optional[Abi] = None) -> Abi:
+    """`names`: C struct name -> name of the Python class; a struct the header declares and `names` lacks is an error.
+    `base`: what the reader got from mi355x_refiners.h, for an extension header that includes it: its structs and constants may be
+    used (the same classes, so that a pointer to one is the type the main header's prototypes take) and are not listed again."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", _blank, text, flags=re.S)
     text = re.sub(r"#\s*ifdef\s+__cplusplus\b.*?#\s*endif", _blank, text, flags=re.S)  # `extern "C" {` and its `}`: not C
     abi = Abi({}, [], {}, {})
+    structs = dict(base.structs) if base else {}  # every struct a field or parameter may name: the base header's, then this header's own
+    constants = dict(base.constants) if base else {}
 
     def fail(pos: int, why: str) -> AbiError:
         return AbiError(f"{where}:{text.count(chr(10), 0, pos) + 1}: {why}")
@@ -59,14 +63,14 @@ def parse(text: str, names: dict, where: str = "header") -> Abi:
         if not d:
             raise fail(m.start(), f"unknown preprocessor line {m.group().strip()!r}")
         if d["name"]:
-            abi.constants[d["name"]] = int(d["value"], 0)
+            abi.constants[d["name"]] = constants[d["name"]] = int(d["value"], 0)
         return _blank(m)
 
     text = re.sub(r"^[ \t]*#[^\n]*", directive, text, flags=re.M)
 
-    def known(base: str, pos: int) -> None:
-        if base not in _SCALARS and base not in abi.structs and base not in ("void", "char"):
-            raise fail(pos, f"unknown type {base!r}")
+    def known(tname: str, pos: int) -> None:
+        if tname not in _SCALARS and tname not in structs and tname not in ("void", "char"):
+            raise fail(pos, f"unknown type {tname!r}")
 
     def fields(body: str, at: int) -> tuple[list, list]:
         out, c_names = [], []
@@ -85,11 +89,11 @@ def parse(text: str, names: dict, where: str = "header") -> Abi:
                 n = _DECLARATOR.fullmatch(s)
                 if not n:
                     raise fail(pos, f"unparseable declarator {s!r}")
-                t = C.c_void_p if f["ptr"] else _SCALARS.get(f["type"]) or abi.structs[f["type"]]
+                t = C.c_void_p if f["ptr"] else _SCALARS.get(f["type"]) or structs[f["type"]]
                 if n["dim"]:
-                    if not n["dim"].isdigit() and n["dim"] not in abi.constants:
+                    if not n["dim"].isdigit() and n["dim"] not in constants:
                         raise fail(pos, f"array dimension {n['dim']!r} is neither a literal nor a #define")
-                    t = t * (int(n["dim"]) if n["dim"].isdigit() else abi.constants[n["dim"]])
+                    t = t * (int(n["dim"]) if n["dim"].isdigit() else constants[n["dim"]])
                 c_names.append(n["name"])
                 out.append((n["name"] + "_" * keyword.iskeyword(n["name"]), t))
         return out, c_names
@@ -102,7 +106,7 @@ def parse(text: str, names: dict, where: str = "header") -> Abi:
                 raise fail(pos, f"unparseable parameter {s.strip()!r}")
             known(p["type"], pos)
             if p["ptr"]:
-                out.append(C.c_char_p if p["type"] == "char" else C.POINTER(abi.structs[p["type"]]) if p["const"] and p["type"] in abi.structs else C.c_void_p)
+                out.append(C.c_char_p if p["type"] == "char" else C.POINTER(structs[p["type"]]) if p["const"] and p["type"] in structs else C.c_void_p)
             elif p["type"] in _SCALARS:
                 out.append(_SCALARS[p["type"]])
             else:
@@ -123,12 +127,12 @@ def parse(text: str, names: dict, where: str = "header") -> Abi:
                 em = re.fullmatch(rf"\s*(\w+)\s*=\s*({_INT})\s*", e)
                 if not em:
                     raise fail(pos, f"enumerator {e.strip()!r} has no integer value")
-                abi.constants[em[1]] = abi.enums[-1][em[1]] = int(em[2], 0)
+                abi.constants[em[1]] = abi.enums[-1][em[1]] = constants[em[1]] = int(em[2], 0)
         elif m["struct"]:
             if m["struct"] not in names:
                 raise fail(pos, f"struct {m['struct']} has no Python name")
             fl, c_names = fields(m["fields"], m.start("fields"))
-            abi.structs[m["struct"]] = type(names[m["struct"]], (C.Structure,), {"_fields_": fl, "_c_fields_": tuple(c_names)})
+            abi.structs[m["struct"]] = structs[m["struct"]] = type(names[m["struct"]], (C.Structure,), {"_fields_": fl, "_c_fields_": tuple(c_names)})
         else:
             if m["ret"] not in ("int", "int64_t") or not m["func"].startswith("mi355x_"):
                 raise fail(pos, f"prototype {m['ret']} {m['func']}(...) is not `int | int64_t mi355x_*`")
@@ -136,6 +140,6 @@ def parse(text: str, names: dict, where: str = "header") -> Abi:
         pos = m.end()
 
 
-def read(names: dict, path: Optional[Path] = None) -> Abi:
+def read(names: dict, path: Optional[Path] = None, base: Optional[Abi] = None) -> Abi:
     path = Path(path or HEADER)
-    return parse(path.read_text(), names, where=path.name)
+    return parse(path.read_text(), names, where=path.name, base=base)

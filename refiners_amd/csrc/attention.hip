@@ -23,63 +23,12 @@
 //     into one private L2 instead of eight.
 //   * softmax in base 2 with the scale folded into one FMA; running max starts at -inf; keys beyond Lk are masked to
 //     -inf in the last tile only; deterministic (no atomics).
-#include "common.cuh"
-#include "../../include/mi355x_refiners.h"
+#include "attn_short_body.cuh"
 #include <type_traits>
 
 namespace {
 
-struct KvP {
-    const char* k;
-    const char* vt;
-    int64_t ldkb, kbsb;    // bytes
-    int64_t ldvtb, vtbsb;  // bytes
-    int Lk;
-    float out_scale;
-};
-
-struct AttnP {
-    int B, H, Lq, nstream;
-    const char* q;
-    int64_t ldqb, qbsb;
-    char* out;
-    int64_t ldob, obsb;
-    float c;  // scale * log2(e)
-    float thr;  // OPT bit 2: a tile leaves the running maximum alone while no score exceeds it by more than thr (= 8 / c: P <= 2^8)
-    KvP kv[2];
-    int qtiles;
-    int xcd;  // 1 = XCD-aware block order
-};
-
-// lane <-> lane ^ 16 and lane <-> lane ^ 32 exchanges as row / half swaps (gfx950): after swap(a = x, b = x), a and b hold the two partners'
-// values in every lane.  Inline asm (the builtin form folds the combine of its two results away when both inputs are the same value);
-// s_nop 1 = the two wait states a VALU write of an operand needs before the swap reads it.
-MI_DEV void xswap16(float& a, float& b) { asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
-MI_DEV void xswap32(float& a, float& b) { asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
-template <bool PL> MI_DEV float group_max(float x) {
-    if constexpr (PL) {
-        float a = x, b = x;
-        xswap16(a, b);
-        a = fmaxf(a, b), b = a;
-        xswap32(a, b);
-        return fmaxf(a, b);
-    } else {
-        x = fmaxf(x, __shfl_xor(x, 16));
-        return fmaxf(x, __shfl_xor(x, 32));
-    }
-}
-template <bool PL> MI_DEV float group_sum(float x) {
-    if constexpr (PL) {
-        float a = x, b = x;
-        xswap16(a, b);
-        a = a + b, b = a;
-        xswap32(a, b);
-        return a + b;
-    } else {
-        x += __shfl_xor(x, 16);
-        return x + __shfl_xor(x, 32);
-    }
-}
+using namespace mi355x_attn;  // KvP, AttnP, the lane-group reductions, the LDS-DMA helpers and the short-K/V tile body (attn_short_body.cuh)
 
 template <typename T, int NW, int NSTREAM, bool GLDS, int NJQ, int RD = 2, int OPT = 0, int ABL = 0, int KVS = 1>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? 2 : 1))) void attn_kernel(const AttnP p) {
@@ -541,19 +490,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(sizeof(
             store16<T>(op + c * EPC, ov);
         }
     }
-}
-
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-MI_DEV rsrc_t make_rsrc(const char* base, int64_t bytes) {  // wave-uniform by construction; readfirstlane makes that provable (otherwise every load sits in a waterfall loop)
-    const uint64_t b = reinterpret_cast<uint64_t>(base);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b), hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
-    const int64_t nb = bytes < 0x7ffffff0 ? bytes : 0x7ffffff0;
-    const int n = __builtin_amdgcn_readfirstlane((int)nb);
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), (short)0, n, 0x00020000);
-}
-// 16 bytes per lane, global -> LDS: lane i lands at lds_wave_base + 16 i; source = descriptor base + voff (per lane) + soff (scalar); bytes beyond the descriptor's range read as zero
-MI_DEV void blds16(rsrc_t rs, char* lds_wave_base, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)lds_wave_base, 16, (int)voff, (int)soff, 0, 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- software-pipelined loop
@@ -1157,9 +1093,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 //     requested, Q K^T runs on two 16-key blocks, the softmax on 8 scores per lane and P V on one 32-key step.
 template <int NSTREAM, int NJQ>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void attn_short_dma_kernel(const AttnP p) {
-    using T = bf16_t;
-    constexpr int D = 64, BKV = 64, NW = 4, BQW = 16 * NJQ, SLOTS = 3, ES = 2, ROWB = D * ES, CPR = ROWB / 16, NTHR = NW * 64, TILEB = 64 * ROWB, STAGE = 2 * TILEB;
-    constexpr int LI = 64 * CPR / NTHR, NS = 2;
+    constexpr int BKV = SHORT_BKV, NW = 4, BQW = 16 * NJQ, SLOTS = SHORT_SLOTS, ROWB = SHORT_ROWB, STAGE = SHORT_SLOTB, NS = 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wid = wave_id();
@@ -1177,31 +1111,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
 
     // ---- every tile of every stream: LDS-DMA into its own slot ----
 #pragma unroll
-    for (int sl = 0; sl < SLOTS; ++sl) {
-        if (sl < ntot) {
-            const int sidx = (NSTREAM > 1 && sl >= nt0) ? 1 : 0;
-            const KvP& kv = p.kv[sidx];
-            const int kv0 = (sidx ? sl - nt0 : sl) * BKV;
-            const bool half = kv.Lk - kv0 <= 32;
-            const rsrc_t krs = make_rsrc(kv.k + (int64_t)b * kv.kbsb + (int64_t)h * ROWB + (int64_t)kv0 * kv.ldkb, (int64_t)63 * kv.ldkb + ROWB);
-            const rsrc_t vrs = make_rsrc(kv.vt + (int64_t)h * D * kv.ldvtb + (int64_t)b * kv.vtbsb + (int64_t)kv0 * ES, (int64_t)(D - 1) * kv.ldvtb + BKV * ES);
-            char* ks = smem + sl * STAGE;
-#pragma unroll
-            for (int it = 0; it < LI; ++it) {
-                const int q = it * NTHR + tid, row = q / CPR, pch = q % CPR;
-                const int cl = pch ^ swz<ROWB>(row);  // the logical chunk this lane's physical slot holds
-                const int key = k_row_key(row);       // LDS rows 0 .. 31 hold keys 0 .. 31 of the tile
-                if (!(half && it * NTHR >= 32 * CPR)) {  // wave-uniform: a half tile has no second K iteration
-                    const uint32_t ko = kv0 + key < kv.Lk ? (uint32_t)(key * (int)kv.ldkb + cl * 16) : 0x80000000u;
-                    blds16(krs, ks + (it * NTHR + wid * 64) * 16, ko, 0);
-                }
-                const int j = row >> 4, a = (row >> 2) & 3, bb = row & 3;
-                const int vrow = 16 * a + 4 * j + bb;
-                const uint32_t vo = kv0 + cl * 8 < kv.Lk ? (uint32_t)(vrow * (int)kv.ldvtb + cl * 16) : 0x80000000u;
-                blds16(vrs, ks + TILEB + (it * NTHR + wid * 64) * 16, vo, 0);
-            }
-        }
-    }
+    for (int sl = 0; sl < SLOTS; ++sl)
+        if (sl < ntot) attn_short_load_slot<NSTREAM>(p, sl, nt0, smem + sl * STAGE, b, h, tid, wid);
 
     frag_t qf[NJQ][NS];
 #pragma unroll
@@ -1215,128 +1126,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     wait_vm0();
     __syncthreads();
 
-    f32x4 res[4][NJQ], o[4][NJQ];
-    float mrun[NJQ], lsum[NJQ];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jq = 0; jq < NJQ; ++jq) res[i][jq] = f32x4{0.f, 0.f, 0.f, 0.f}, o[i][jq] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int jq = 0; jq < NJQ; ++jq) mrun[jq] = -INFINITY, lsum[jq] = 0.f;
-
-    auto finish = [&](float out_scale) {
-#pragma unroll
-        for (int jq = 0; jq < NJQ; ++jq) {
-            const float l = group_sum<true>(lsum[jq]);
-            const float inv = out_scale / l;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                res[i][jq] += o[i][jq] * inv;
-                o[i][jq] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-            mrun[jq] = -INFINITY, lsum[jq] = 0.f;
-        }
-    };
-
-    auto tile = [&](const char* ks, int kv0, int Lk, auto halfc) {
-        constexpr int TT = decltype(halfc)::value ? 2 : 4;  // 16-key blocks of the tile that hold valid keys
-        const char* vs = ks + TILEB;
-        f32x4 st[TT][NJQ];
-#pragma unroll
-        for (int t = 0; t < TT; ++t) {
-#pragma unroll
-            for (int jq = 0; jq < NJQ; ++jq) st[t][jq] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const frag_t kf = lds_read_frag(ks, tile_off<ROWB>(16 * t + c16, 4 * s + g));
-#pragma unroll
-                for (int jq = 0; jq < NJQ; ++jq) mma_step<T>(st[t][jq], kf, qf[jq][s]);
-            }
-        }
-        if (kv0 + BKV > Lk) {
-#pragma unroll
-            for (int t = 0; t < TT; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (kv0 + k_row_key(16 * t + 4 * g + r) >= Lk) {
-#pragma unroll
-                        for (int jq = 0; jq < NJQ; ++jq) st[t][jq][r] = -INFINITY;
-                    }
-                }
-        }
-#pragma unroll
-        for (int jq = 0; jq < NJQ; ++jq) {
-            float mx = st[0][jq][0];
-#pragma unroll
-            for (int t = 0; t < TT; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) mx = fmaxf(mx, st[t][jq][r]);
-            mx = group_max<true>(mx);
-            const float mnew = fmaxf(mrun[jq], mx);
-            const float alpha = fast_exp2((mrun[jq] - mnew) * p.c);
-            const float mc = mnew * p.c;
-            float ps = 0.f;
-#pragma unroll
-            for (int t = 0; t < TT; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float e = fast_exp2(st[t][jq][r] * p.c - mc);
-                    st[t][jq][r] = e;
-                    ps += e;
-                }
-            lsum[jq] = lsum[jq] * alpha + ps;
-            mrun[jq] = mnew;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[i][jq] *= alpha;
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < TT / 2; ++s2) {
-            frag_t pb[NJQ];
-#pragma unroll
-            for (int jq = 0; jq < NJQ; ++jq) {
-                bf16x8 pk;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    pk[r] = (bf16_t)st[2 * s2][jq][r];
-                    pk[4 + r] = (bf16_t)st[2 * s2 + 1][jq][r];
-                }
-                pb[jq] = __builtin_bit_cast(frag_t, pk);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const frag_t vf = lds_read_frag(vs, tile_off<ROWB>(16 * i + c16, 4 * s2 + g));
-#pragma unroll
-                for (int jq = 0; jq < NJQ; ++jq) mma_step<T>(o[i][jq], vf, pb[jq]);
-            }
-        }
-    };
-
-#pragma unroll
-    for (int sl = 0; sl < SLOTS; ++sl) {
-        if (sl < ntot) {
-            const int sidx = (NSTREAM > 1 && sl >= nt0) ? 1 : 0;
-            if (NSTREAM > 1 && sl == nt0) finish(p.kv[0].out_scale);  // first tile of the second stream: close the first
-            const int Lk = p.kv[sidx].Lk;
-            const int kv0 = (sidx ? sl - nt0 : sl) * BKV;
-            if (Lk - kv0 <= 32) tile(smem + sl * STAGE, kv0, Lk, std::true_type{});
-            else tile(smem + sl * STAGE, kv0, Lk, std::false_type{});
-        }
-    }
-    finish(p.kv[NSTREAM - 1].out_scale);
-
-#pragma unroll
-    for (int jq = 0; jq < NJQ; ++jq) {
-        const int qr = q0 + 16 * jq + c16;
-        if (qr >= p.Lq) continue;
-        T* op = reinterpret_cast<T*>(p.out + (int64_t)b * p.obsb + (int64_t)qr * p.ldob + (int64_t)h * ROWB) + 16 * g;
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            Vec16<T> ov;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) ov.set(e, res[(c * 8 + e) >> 2][jq][e & 3]);
-            store16<T>(op + c * 8, ov);
-        }
-    }
+    attn_short_tiles<NSTREAM, NJQ>(p, [&](int sl) { return smem + sl * STAGE; }, qf, b, h, q0, lane);
 }
 
 int g_attn_short_q16 = 0;  // short-K/V kernel with 64-query workgroups: 0 = where the grid of 128-query workgroups is short (<= 640), 1 = never, 2 = always
@@ -1560,8 +1350,6 @@ int launch_attn_t(const AttnP& p, hipStream_t stream) {
     return nw == 2 ? launch_attn_nw<T, 2>(p, stream) : launch_attn_nw<T, 4>(p, stream);
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int mi355x_attention_set_nw(int v) {
@@ -1592,41 +1380,8 @@ extern "C" int mi355x_attention_set_pipeline(int tiles_in_flight, int xcd_aware)
 }
 
 extern "C" int mi355x_attention(const mi355x_attn_args* a, void* stream) {
-    if (!a || !a->q || !a->out) return MI355X_EARG;
-    if (a->dtype != MI355X_F32 && a->dtype != MI355X_BF16) return MI355X_EDTYPE;
-    if (a->D != 64 || a->B <= 0 || a->H <= 0 || a->Lq <= 0 || a->nstream < 1 || a->nstream > 2) return MI355X_ESHAPE;
-    const int es = a->dtype == MI355X_F32 ? 4 : 2;
-    if (!al16(a->q) || !al16(a->out) || (a->ldq * es) % 16 || (a->ldo * es) % 16 || (a->q_batch_stride * es) % 16 ||
-        (a->o_batch_stride * es) % 16)
-        return MI355X_ESHAPE;
     AttnP p{};
-    p.B = a->B;
-    p.H = a->H;
-    p.Lq = a->Lq;
-    p.nstream = a->nstream;
-    p.q = static_cast<const char*>(a->q);
-    p.ldqb = a->ldq * es;
-    p.qbsb = a->q_batch_stride * es;
-    p.out = static_cast<char*>(a->out);
-    p.ldob = a->ldo * es;
-    p.obsb = a->o_batch_stride * es;
-    p.c = a->scale * 1.44269504088896340736f;
-    p.thr = p.c > 0.f ? 8.0f / p.c : 0.f;
-    for (int s = 0; s < a->nstream; ++s) {
-        const mi355x_kv_stream& k = a->kv[s];
-        if (!k.k || !k.vt || k.Lk <= 0) return MI355X_ESHAPE;
-        if (!al16(k.k) || !al16(k.vt) || (k.ldk * es) % 16 || (k.ldvt * es) % 16 || (k.k_batch_stride * es) % 16 ||
-            (k.vt_batch_stride * es) % 16)
-            return MI355X_ESHAPE;
-        p.kv[s].k = static_cast<const char*>(k.k);
-        p.kv[s].vt = static_cast<const char*>(k.vt);
-        p.kv[s].ldkb = k.ldk * es;
-        p.kv[s].kbsb = k.k_batch_stride * es;
-        p.kv[s].ldvtb = k.ldvt * es;
-        p.kv[s].vtbsb = k.vt_batch_stride * es;
-        p.kv[s].Lk = k.Lk;
-        p.kv[s].out_scale = k.out_scale;
-    }
+    if (const int err = attn_params(a, p)) return err;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (a->dtype == MI355X_F32) return launch_attn_t<float>(p, st);
     return launch_attn_t<bf16_t>(p, st);

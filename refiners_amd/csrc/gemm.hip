@@ -84,15 +84,17 @@ extern "C" int mi355x_epoch_bump(int32_t* epoch, void* stream) {
     return hipGetLastError() == hipSuccess ? MI355X_OK : MI355X_ELAUNCH;
 }
 
-extern "C" int mi355x_gemm(const mi355x_gemm_args* a, void* stream) {
+// mi355x_gemm_args -> GemmP: every check of the contract that does not depend on the tile configuration (0, or the MI355X_E* code of the refusal).
+// Shared with mi355x_gemm_attention (gemm_xattn.hip), which takes the same struct.
+int mi355x::gemm_params(const mi355x_gemm_args* a, GemmP& p, bool need_out) {
     if (!a) return MI355X_EARG;
     const bool has_t = a->out_t != nullptr;
-    if (!a->out && !(has_t && a->nt_begin == 0)) return MI355X_EARG;
+    if (need_out && !a->out && !(has_t && a->nt_begin == 0)) return MI355X_EARG;
     if (a->dtype != MI355X_F32 && a->dtype != MI355X_BF16) return MI355X_EDTYPE;
     if (a->M <= 0 || a->N <= 0 || a->nseg < 1 || a->nseg > MI355X_MAX_SEG) return MI355X_ESHAPE;
     const int es = a->dtype == MI355X_F32 ? 4 : 2;
     const int bke = 128 / es;  // elements per K block
-    GemmP p{};
+    p = GemmP{};
     p.M = a->M;
     p.N = a->N;
     p.nseg = a->nseg;
@@ -237,6 +239,12 @@ extern "C" int mi355x_gemm(const mi355x_gemm_args* a, void* stream) {
             p.partial = static_cast<float*>(a->ws);
         }
     }
+    return MI355X_OK;
+}
+
+extern "C" int mi355x_gemm(const mi355x_gemm_args* a, void* stream) {
+    GemmP p;
+    if (const int err = gemm_params(a, p)) return err;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int ncu = cu_count();
     const bool sk_scratch = a->sk_ws && a->sk_flags && a->sk_slots > 0 && (reinterpret_cast<uintptr_t>(a->sk_ws) & 15) == 0;

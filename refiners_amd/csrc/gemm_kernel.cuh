@@ -42,6 +42,7 @@
 //     workgroups instead of 192 in front of 480 tiles that fill the chip's 512 resident slots;
 //   * bf16 -> v_mfma_f32_16x16x32_bf16, f32 (parity mode) -> v_mfma_f32_16x16x4_f32; identical LDS image.
 #pragma once
+#include "attn_short_body.cuh"
 #include "gemm_epilogue.cuh"
 #include "gemm_lora_producer.cuh"
 #include "gemm_tiles.cuh"
@@ -68,13 +69,31 @@ namespace mi355x {
 #ifndef MI355X_LORA64_WAVES
 #define MI355X_LORA64_WAVES 4  // waves per SIMD the 64 x 64 LoRA instance leaves room for (the plain instance: 84 registers = 5; at 5 the LoRA instance spills 74 registers and the step loses 1.3 %: 24.15 -> 24.47 ms, profiles/r06_zf_ab_lora64_waves.log)
 #endif
-template <typename T, int BM, int BN, bool LORA> constexpr int gemm_min_waves() {
+template <typename T, int BM, int BN, bool LORA, bool XATTN = false> constexpr int gemm_min_waves() {
+    if (XATTN) return 3;  // three workgroups per CU: the LDS plan of the cross-attention form (see XATTN below)
     if (!LORA || sizeof(T) != 2) return 1;
     return BM * BN == 128 * 128 ? 2 : BM * BN == 64 * 64 ? MI355X_LORA64_WAVES : BM == 128 ? 3 : 2;
 }
 
-template <typename T, int BM, int BN, int WM, int WN, bool CONV, int NSTAGE, int KG = 1, bool LORA = false>
-__global__ __launch_bounds__(WM* WN * 64 * KG) __attribute__((amdgpu_waves_per_eu(gemm_min_waves<T, BM, BN, LORA>()))) void gemm_kernel(const GemmP p) {
+// XATTN (the cross-attention form, mi355x_gemm_attention: bf16, 64 x 64 tiles, two stages): the GEMM is the Q projection of a cross-attention against at most three
+// 64-key tiles of step-constant K / V^T, a column tile is one head (D = 64 = BN), and the workgroup that has finished a Q tile attends with it at once: Q never
+// goes to memory, the attention launch disappears.  LDS per phase (bytes; `ring` = the two stages, 32 768):
+//   K loop     [0, ring) stages | rowstat 512 (LayerNorm) | lora_b0 4 096 (LORA) | slot 0 16 384: the first K / V^T tile, by LDS-DMA from the kernel's entry
+//   after it   one barrier (every wave has read its last fragments), then the remaining tiles go into the drained ring by LDS-DMA: tile 1 at 0, tile 2 at
+//              16 384 (K rows at + 0, V^T rows at + 8 192); they land while the LoRA term and the epilogue arithmetic run
+//   exchange   the epilogue rounds Q to bf16 as the store would and writes the 64 x 64 image (128-byte swizzled rows, 8 192 bytes) where no tile lies: at 16 384
+//              with at most two tiles; with three, tiles 1 and 2 are HALF tiles (the host refuses other launches) whose K rows 32 .. 63 are never written,
+//              and Q rows 0 .. 31 / 32 .. 63 take those two 4 096-byte holes (at 4 096 and 20 480); vmcnt(0) + one barrier
+//   tail       each wave reads the fragments of its 16 queries and runs attn_short_tiles (NJQ = 1) on slot 0 + the ring; no further barrier
+// 53 760 bytes with LayerNorm and LoRA: three workgroups per CU (161 280 of 163 840).
+struct GemmXP : GemmP {
+    mi355x_attn::AttnP xa;
+};
+constexpr int XATTN_SLOT0 = mi355x_attn::SHORT_SLOTB;  // bytes the cross-attention form adds behind lora_b0
+
+template <typename T, int BM, int BN, int WM, int WN, bool CONV, int NSTAGE, int KG = 1, bool LORA = false, bool XATTN = false>
+__global__ __launch_bounds__(WM* WN * 64 * KG) __attribute__((amdgpu_waves_per_eu(gemm_min_waves<T, BM, BN, LORA, XATTN>()))) void gemm_kernel(const std::conditional_t<XATTN, GemmXP, GemmP> p) {
+    static_assert(!XATTN || (sizeof(T) == 2 && BM == 64 && BN == 64 && WM == 2 && WN == 2 && NSTAGE == 2 && KG == 1 && !CONV), "cross-attention form: bf16, 64 x 64 tiles, two stages");
     constexpr int NW = WM * WN;           // waves per K group
     constexpr int NTHR = NW * 64;         // threads per K group: the loader geometry
     constexpr int NTHR_ALL = NTHR * KG;   // threads per workgroup
@@ -90,6 +109,7 @@ __global__ __launch_bounds__(WM* WN * 64 * KG) __attribute__((amdgpu_waves_per_e
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* rowstat = reinterpret_cast<float*>(smem + KG * NSTAGE * STAGE);  // [BM][2] (mean, rstd) of the tile's rows (LayerNorm consumer)
     char* const lora_b0 = smem + KG * NSTAGE * STAGE + (p.ln_stats ? BM * 8 : 0);  // LORA: [BN][32 ranks] of T, the first up-projection chunk (staged by the prologue)
+    char* const xa_slot0 = lora_b0 + (LORA ? BN * LORA_RC * (int)sizeof(T) : 0);    // XATTN: the first K / V^T tile
 
     const int tid_all = threadIdx.x, wid_all = wave_id();
     const int kg = KG > 1 ? wid_all / NW : 0;
@@ -174,7 +194,7 @@ __global__ __launch_bounds__(WM* WN * 64 * KG) __attribute__((amdgpu_waves_per_e
     }
     if (tm >= p.tiles_m || tn >= p.tiles_n) return;
     const int m0 = tm * BM, n0 = tn * BN;
-    const bool tr = !CONV && !ttile && n0 >= p.nt_begin;  // workgroup-uniform: this tile is stored transposed (operand roles swapped)
+    const bool tr = !XATTN && !CONV && !ttile && n0 >= p.nt_begin;  // workgroup-uniform: this tile is stored transposed (operand roles swapped)
 
     // ---- per-thread loader coordinates (fixed for the whole K loop) ----
     // Exactly one operand's rows are permuted inside each wave's 16*T-row span (see the header): the weights' normally, the
@@ -371,6 +391,15 @@ __global__ __launch_bounds__(WM* WN * 64 * KG) __attribute__((amdgpu_waves_per_e
     for (int s0 = 0; s0 < D; ++s0)
         if (s0 < my_kb) issue(s0);
 
+    // XATTN: this tile is head tn of batch element m0 / Lq (Lq % 64 == 0: a row tile never straddles two); its first K / V^T tile is requested now
+    int xa_b = 0, xa_nt0 = 0, xa_ntot = 0;
+    if constexpr (XATTN) {
+        xa_b = m0 / p.xa.Lq;
+        xa_nt0 = (p.xa.kv[0].Lk + 63) / 64;
+        xa_ntot = xa_nt0 + (p.xa.nstream > 1 ? (p.xa.kv[1].Lk + 63) / 64 : 0);
+        mi355x_attn::attn_short_load_slot<0>(p.xa, 0, xa_nt0, xa_slot0, xa_b, tn, tid, wid);
+    }
+
     if (p.ln_stats) ln_rowstat<BM, NTHR_ALL>(p, m0, tid_all, rowstat);
 
     // ---- main loop, software-pipelined through REGISTERS as well: the MFMAs of one half K block (32 bf16 / 16 f32 deep) run
@@ -529,6 +558,16 @@ __global__ __launch_bounds__(WM* WN * 64 * KG) __attribute__((amdgpu_waves_per_e
         else mainloop(std::false_type{});
     }
 
+    if constexpr (XATTN) {
+        // every wave is done with the stage buffers (the loop's last phase read a stage): the remaining K / V^T tiles go there, and land behind the LoRA term
+        // and the epilogue arithmetic
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+#pragma unroll
+        for (int sl = 1; sl < mi355x_attn::SHORT_SLOTS; ++sl)
+            if (sl < xa_ntot) mi355x_attn::attn_short_load_slot<0>(p.xa, sl, xa_nt0, smem + (sl - 1) * mi355x_attn::SHORT_SLOTB, xa_b, tn, tid, wid);
+    }
+
     if constexpr (LORA) {
         // ---- up-projection: acc += T(t) . (s B_cat)^T, 32 ranks per MMA chunk; t comes from this row block's producers ----------------------
         if (lora_tail && !(p.lora_dbg & 8)) {
@@ -668,7 +707,80 @@ __global__ __launch_bounds__(WM* WN * 64 * KG) __attribute__((amdgpu_waves_per_e
         }
     }
 
-    tile_epilogue<T, MT, NT, BM, CONV>(p, acc, rowstat, m0, n0, wm, wn, lane, tr, split);
+    if constexpr (XATTN) {
+        // ---- Q exchange: the values tile_epilogue would store (folded LayerNorm or bias, rounded to bf16), as the tile's 128-byte swizzled rows in LDS ----
+        constexpr int RUN = 4 * NT;
+        static_assert(RUN == 8, "a lane's run is one 16-byte chunk of a Q row");
+        const int nl = wn * WNE + RUN * g, n = n0 + nl;
+        auto q_off = [&](int row, int chunk) {  // (see the LDS plan above)
+            return xa_ntot == 3 ? 4096 + (row >> 5) * 16384 + tile_off<128>(row & 31, chunk) : 16384 + tile_off<128>(row, chunk);
+        };
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+            const int mrow = wm * WME + 16 * i + c16;
+            float v[RUN];
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[4 * j + r] = acc[i][j][r];
+            if (p.ln_stats) {  // y = rstd * (acc - mean * s[n]) + c[n]   (c carries the Linear's bias)
+                const float mean = rowstat[2 * mrow], rstd = rowstat[2 * mrow + 1];
+#pragma unroll
+                for (int c = 0; c < RUN / 4; ++c) {
+                    const f32x4 sv = *reinterpret_cast<const f32x4*>(p.ln_s + n + 4 * c), cv = *reinterpret_cast<const f32x4*>(p.ln_c + n + 4 * c);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[4 * c + e] = rstd * (v[4 * c + e] - mean * sv[e]) + cv[e];
+                }
+            } else if (p.bias) {
+                const Vec16<T> bv = load16<T>(reinterpret_cast<const T*>(p.bias) + n);
+#pragma unroll
+                for (int e = 0; e < RUN; ++e) v[e] += bv.get(e);
+            }
+            Vec16<T> ov;
+#pragma unroll
+            for (int e = 0; e < RUN; ++e) ov.set(e, v[e]);
+            *reinterpret_cast<decltype(ov.v)*>(smem + q_off(mrow, nl / 8)) = ov.v;
+        }
+        wait_vm0();  // this thread's pieces of the late tiles (and of slot 0, long ago) have landed
+        __syncthreads();
+        // ---- attention tail: wave `wid` owns queries m0 % Lq + 16 wid .. + 15 of head tn ----
+        const int qrow = 16 * wid + c16;
+        frag_t qf[1][2];
+#pragma unroll
+        for (int sidx = 0; sidx < 2; ++sidx) qf[0][sidx] = lds_read_frag(smem, q_off(qrow, 4 * sidx + g));
+        const int q0 = m0 - xa_b * p.xa.Lq + 16 * wid;
+        mi355x_attn::attn_short_tiles<0, 1>(p.xa, [&](int sl) { return sl == 0 ? xa_slot0 : smem + (sl - 1) * mi355x_attn::SHORT_SLOTB; }, qf, xa_b, tn, q0, lane);
+        return;
+    } else {
+        tile_epilogue<T, MT, NT, BM, CONV>(p, acc, rowstat, m0, n0, wm, wn, lane, tr, split);
+    }
+}
+
+// The cross-attention form's launch (gemm_xattn.hip): one dispatch of producers (LORA) + tiles, as launch_cfg's
+template <bool LORA>
+int launch_xattn(const GemmP& p0, const mi355x_attn::AttnP& xa, hipStream_t stream) {
+    using T = bf16_t;
+    constexpr int BM = 64, BN = 64;
+    constexpr int LDS = 2 * (BM + BN) * 128 + BM * 8 + (LORA ? BN * LORA_RC * (int)sizeof(T) : 0) + XATTN_SLOT0;
+    static_assert(3 * LDS <= 160 * 1024, "three workgroups per CU");
+    auto kfn = gemm_kernel<T, BM, BN, 2, 2, false, 2, 1, LORA, true>;
+    static bool attr_set[64] = {};  // per device: the attribute belongs to the device's copy of the code object
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        attr_set[dev] = true;
+    }
+    GemmXP q;
+    static_cast<GemmP&>(q) = p0;
+    q.xa = xa;
+    plan_grid(q, BM, BN, false, 1);
+    q.lora_dbg = 0;
+    q.lora_tt = 0;  // one column group: t comes from producers
+    q.lp_blocks = !LORA ? 0 : ((q.M + LORA_PM - 1) / LORA_PM * q.lora_groups + 7) / 8 * 8;
+    const int grid = q.pf_blocks + q.lp_blocks + q.grid0;
+    hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), q.ln_stats ? LDS : LDS - BM * 8, stream, q);
+    return hipGetLastError() == hipSuccess ? MI355X_OK : MI355X_ELAUNCH;
 }
 
 template <typename T, int BM, int BN, int WM, int WN, bool CONV, int NSTAGE, int KG = 1, bool LORA = false>
@@ -783,6 +895,7 @@ int launch_tile(const GemmP& p, hipStream_t stream) {
     }
 }
 
+int gemm_params(const mi355x_gemm_args* a, GemmP& p, bool need_out = true);  // (gemm.hip)
 int launch_conv_f32(const GemmP& p, hipStream_t stream);
 int launch_conv_bf16(const GemmP& p, hipStream_t stream);
 

@@ -61,6 +61,11 @@ class Lowering:
         # GroupNorm statistics from the epilogue of the convolution / GEMM that produces the normalised tensor (mi355x_gemm_args.colstats_out):
         # the statistics pass over that tensor disappears (2 launches per GroupNorm instead of 3); 0 = always the three-kernel GroupNorm
         self.gn_stats = os.environ.get("REFINERS_AMD_GN_STATS", "1") != "0"
+        # a cross-attention folded into its Q projection (mi355x_gemm_attention: one launch, Q never written; BlockLowering.xattn_foldable):
+        # REFINERS_AMD_XATTN_FOLD = 0 keeps the two launches, 1 folds the sites whose Q projection runs on the 64 x 64 tile anyway, 2 folds every
+        # eligible site (moves the others' Q projection to that tile: A/B runs).  Unset: 1 on a device, 0 in a dry run on the meta device (like the
+        # in-launch LoRA, a decision for real launches: the dry-run program stays the device-independent one)
+        self.xattn_fold = int(os.environ.get("REFINERS_AMD_XATTN_FOLD") or ("0" if device.type == "meta" else "1"))
         self._cs_buf: list[Tensor] = []
         self._lsync: Any = None          # native.LoraSync: the epoch word every program of this lowering bumps once per replay
         self._sk = native.StreamK(device)  # scratch of this lowering's stream-K launches (tile 8): allocated by the first one, shared by all (one stream)
@@ -356,13 +361,17 @@ class Lowering:
 
     def linear(self, x: Any, spec: LinSpec, *, res: Optional[Tensor] = None, out: Optional[Tensor] = None,
                rows: Optional[int] = None, lora_t: Optional[Tensor] = None, gelu: bool = False, out_kblocked: bool = False,
-               ln: Optional[tuple] = None, stats_out: Optional[Tensor] = None, colstats: Any = None) -> Tensor:
+               ln: Optional[tuple] = None, stats_out: Optional[Tensor] = None, colstats: Any = None, attn: Optional[tuple] = None) -> Optional[Tensor]:
         """out[M, N(/2 if geglu)] = epi(x W^T + b (+ LoRA) (+ res)).  `colstats` = colstats_for(...): also write the output's GroupNorm statistics.  `lora_t` lets callers share one down-projection
         launch between Linears that read the same x.  `ln` = (stats, LayerNorm node): x is the UN-normalised tensor and the
-        LayerNorm is applied inside this launch (ln_fold); `stats_out`: also write the output rows' statistics."""
+        LayerNorm is applied inside this launch (ln_fold); `stats_out`: also write the output rows' statistics.
+        `attn` = native.attention_args(None, ...): the cross-attention this Linear is the Q projection of runs inside the launch (native.gemm); nothing is returned."""
         M = x.shape[0]
         n_cols = spec.N // 2 if spec.geglu else spec.N
-        if out is None:
+        xa = dict(attn=attn, tile=4) if attn is not None else {}
+        if attn is not None:
+            assert out is None and res is None and not spec.geglu and (spec.lora is None or (spec.lora.a_kb is not None and self.lora_inlaunch))
+        elif out is None:
             out = self.pool.get(M, n_cols)
         cso = colstats
         if ln is not None:
@@ -374,7 +383,7 @@ class Lowering:
                 lo = ([(0, al)], spec.lora.bs_r, als, alc)
                 sy = self.lora_sync(1, M, spec.lora.R)
             native.gemm([(x, self.kblocked(wl))], out, res=res, geglu=spec.geglu, gelu=gelu, out_kblocked=out_kblocked, ln=(stats, ls, lc, float(node.eps)),
-                        stats_out=stats_out, lora=lo, lora_sync=sy, colstats_out=cso)
+                        stats_out=stats_out, lora=lo, lora_sync=sy, colstats_out=cso, **xa)
             if sy is not None:
                 self.pool.put(sy[0])
             return out
@@ -382,7 +391,7 @@ class Lowering:
             # LoraAdapter = Sum(target, loras) as ONE launch: producer workgroups compute x A_cat^T once per row block, the up-projections are the tiles' last K steps
             sy = self.lora_sync(1, M, spec.lora.R)
             native.gemm([(x, self.kblocked(spec.w))], out, bias=spec.b, res=res, geglu=spec.geglu, gelu=gelu, out_kblocked=out_kblocked, stats_out=stats_out,
-                        lora=([(0, spec.lora.a_kb)], spec.lora.bs_r), lora_sync=sy, colstats_out=cso)
+                        lora=([(0, spec.lora.a_kb)], spec.lora.bs_r), lora_sync=sy, colstats_out=cso, **xa)
             self.pool.put(sy[0])
             return out
         segs = [(x, self.kblocked(spec.w))]
@@ -390,7 +399,7 @@ class Lowering:
         if spec.lora is not None:
             t = lora_t if lora_t is not None else self.lora_down(x, spec.lora)
             segs.append((t, spec.lora.bs_cat))
-        native.gemm(segs, out, bias=spec.b, res=res, geglu=spec.geglu, gelu=gelu, out_kblocked=out_kblocked, stats_out=stats_out, colstats_out=cso)
+        native.gemm(segs, out, bias=spec.b, res=res, geglu=spec.geglu, gelu=gelu, out_kblocked=out_kblocked, stats_out=stats_out, colstats_out=cso, **xa)
         if t is not None and lora_t is None:
             self.pool.put(t)
         return out

@@ -143,12 +143,7 @@ class BlockLowering(Lowering):
         kind = self.head_kernel(d)
         if kind is not None:
             q3 = q.as_strided((B, Lq, C), (Lq * q.stride(0), q.stride(0), 1))
-            st = []
-            for k, vt, Lk, osc in streams:
-                lkp = k.shape[0] // B
-                kv = k.as_strided((B, lkp, C), (lkp * k.stride(0), k.stride(0), 1))  # k may be a column slice of a packed [Q|K] buffer
-                lv = vt.shape[1] // B
-                st.append((kv, vt.as_strided((C, B, lv), (vt.stride(0), lv, 1)), Lk, osc))  # vt rows may be padded (stride > B lv)
+            st = self._stream_views(B, C, streams)
             if kind == "flash64":
                 native.attention(q3, out.view(B, Lq, C), heads, st)
                 return out
@@ -199,6 +194,35 @@ class BlockLowering(Lowering):
         self.python(run, f"torch_sdpa_d{d}")
         self.stats["fallback_nodes"].append(f"SDPA(head_dim={d})")
         return out
+
+    @staticmethod
+    def _stream_views(B: int, C: int, streams: list) -> list:
+        """(k [B, Lkp, C], vt [C, B, Lkp], Lk, out_scale) views of sdpa's streams, as native.attention takes them."""
+        st = []
+        for k, vt, Lk, osc in streams:
+            lkp = k.shape[0] // B
+            kv = k.as_strided((B, lkp, C), (lkp * k.stride(0), k.stride(0), 1))  # k may be a column slice of a packed [Q|K] buffer
+            lv = vt.shape[1] // B
+            st.append((kv, vt.as_strided((C, B, lv), (vt.stride(0), lv, 1)), Lk, osc))  # vt rows may be padded (stride > B lv)
+        return st
+
+    def xattn_foldable(self, qspec: LinSpec, M: int, B: int, heads: int, streams: list, ln_fused: bool) -> bool:
+        """May this cross-attention run inside its Q projection's launch (mi355x_gemm_attention, include/mi355x_refiners_xattn.h)?  The Q Linear must be a
+        plain one-launch GEMM (bias, folded LayerNorm, in-launch LoRA of stacked rank 32) on the 64 x 64 tile, the attention one the short bf16 LDS-DMA
+        kernel would take (heads of 64, at most three key tiles) whose tiles fit the fused kernel's LDS plan, a row tile inside one batch element.
+        Everything else keeps the two launches: float32 parity mode, SD1.5's heads, ELLA's longer token streams, stacked ranks above 32, the two-launch
+        LoRA path, and -- unless the lever says 2 -- shape classes whose Q projection the tuning table or the heuristic runs on another tile."""
+        if not self.xattn_fold or self.dtype != torch.bfloat16 or qspec.geglu or qspec.N != heads * 64 or qspec.K % 64 or M % B or (M // B) % 64:
+            return False
+        lora = qspec.lora
+        if lora is not None and not (lora.a_kb is not None and self.lora_inlaunch and lora.R == 32):
+            return False
+        nt = [(Lk + 63) // 64 for (_k, _vt, Lk, _osc) in streams]
+        if len(nt) > 2 or sum(nt) > 3 or min(Lk for (_k, _vt, Lk, _osc) in streams) < 1:
+            return False
+        if sum(nt) == 3 and not (nt == [2, 1] and streams[0][2] - 64 <= 32 and streams[1][2] <= 32):
+            return False
+        return self.xattn_fold == 2 or native.xattn_tile_ok(M, qspec.N, qspec.K, self.dtype, ln_fused, lora is not None)
 
     def head_kernel(self, d: int) -> Optional[str]:
         """Which attention kernel serves head dim d: mi355x_attention (64), mi355x_attention_general (<= 160, 16-byte rows), none."""
@@ -419,14 +443,22 @@ class BlockLowering(Lowering):
             self.stats["ip_sites"] += 1
         qspec = self.linear_spec(qn)
         M, C = x.shape[0], qspec.N
-        if self.ln_fusable(stats, qspec):
-            q = self.linear(x, qspec, ln=(stats, ln))
+        ln_fused = self.ln_fusable(stats, qspec)
+        fold = self.head_kernel(C // heads) == "flash64" and self.xattn_foldable(qspec, M, B, heads, streams, ln_fused)
+        at = None
+        if fold:  # Q projection and attention as one launch: q is never allocated
+            o = self.pool.get(M, C)
+            at = native.attention_args(None, o.view(B, M // B, C), heads, self._stream_views(B, C, streams))
+            self.stats["xattn_fold_sites"] = self.stats.get("xattn_fold_sites", 0) + 1
+        if ln_fused:
+            q = self.linear(x, qspec, ln=(stats, ln), attn=at)
         else:
             h = self.layernorm(x, ln)
-            q = self.linear(h, qspec)
+            q = self.linear(h, qspec, attn=at)
             self.pool.put(h)
-        o = self.sdpa(q, B, heads, streams, v_plain=plains if plains[0] is not None else None)
-        self.pool.put(q)
+        if not fold:
+            o = self.sdpa(q, B, heads, streams, v_plain=plains if plains[0] is not None else None)
+            self.pool.put(q)
         self.linear(o, self.linear_spec(on), res=x, out=x, stats_out=stats_out)
         self.pool.put(o)
         return x

@@ -84,6 +84,8 @@ _abi_reference_only = abi.read(REFERENCE_ONLY_STRUCT_NAMES, abi.HEADER.parent / 
 globals().update({cls.__name__: cls for cls in _abi_reference_only.structs.values()})
 #: include/mi355x_refiners_cond_input.h, step-constant UNet input channels (inpainting, IC-Light; no structs)
 _abi_cond_input = abi.read({}, abi.HEADER.parent / "mi355x_refiners_cond_input.h")
+#: include/mi355x_refiners_xattn.h, a cross-attention folded into its Q projection (no structs of its own: it takes GemmArgs and AttnArgs)
+_abi_xattn = abi.read({}, abi.HEADER.parent / "mi355x_refiners_xattn.h", base=_abi)
 _K = _abi.constants
 
 #: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
@@ -106,6 +108,8 @@ EXPORTS_LINEART = list(_abi_lineart.functions)
 EXPORTS_REFERENCE_ONLY = list(_abi_reference_only.functions)
 #: every symbol include/mi355x_refiners_cond_input.h declares
 EXPORTS_COND_INPUT = list(_abi_cond_input.functions)
+#: every symbol include/mi355x_refiners_xattn.h declares
+EXPORTS_XATTN = list(_abi_xattn.functions)
 #: exported for probing and A/B runs, by design not in the header (no stable contract): name -> (restype, argtypes), applied by load() like the header's
 UNSTABLE = {
     "mi355x_set_option": (C.c_int, [C.c_char_p, C.c_int]),
@@ -201,7 +205,7 @@ def load(path: Optional[Path] = None) -> C.CDLL:
         lib = C.CDLL(str(p))
     except OSError as e:  # e.g. no HIP runtime on this machine
         raise NativeError(f"cannot load {p}: {e}") from e
-    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **_abi_mvanet.functions, **_abi_dinov2.functions, **_abi_ella.functions, **_abi_lineart.functions, **_abi_reference_only.functions, **_abi_cond_input.functions, **UNSTABLE}.items():
+    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **_abi_mvanet.functions, **_abi_dinov2.functions, **_abi_ella.functions, **_abi_lineart.functions, **_abi_reference_only.functions, **_abi_cond_input.functions, **_abi_xattn.functions, **UNSTABLE}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.mi355x_abi_version() != ABI_VERSION:
@@ -546,8 +550,11 @@ def gemm(
     lora: Optional[tuple[Sequence[tuple[int, "KBlocked"]], Tensor]] = None,
     lora_sync: Optional[tuple] = None,
     colstats_out: Optional[Tensor] = None,
+    attn: Optional[tuple] = None,
 ) -> Optional[Tensor]:
     """out[M,N] = epi(sum_s x_s @ w_s^T) for plain row-major 2-D segments (x_s: [M,K_s], w_s: [N,K_s]).
+    attn = (AttnArgs, keep-alive) from attention_args(None, ...): this GEMM is the Q projection of that cross-attention and both run as ONE
+    launch, mi355x_gemm_attention (include/mi355x_refiners_xattn.h); `out` is None, Q is never written.
     weight_operand="x" marks launches whose PARAMETERS sit in the x slot (transposed projections) for link_weight_prefetch.
     out_t / nt_begin: columns >= nt_begin are written transposed, out_t[n - nt_begin][m] (`out` then has nt_begin columns).
     ln = (stats [parts, M, 2] float32, s [N] float32, c [N] float32, eps): LayerNorm of x folded into this launch (see the header);
@@ -575,7 +582,7 @@ def gemm(
         assert out_t.dim() == 2 and out_t.stride(1) == 1 and out_t.shape[0] >= a.N - nt_begin and out_t.shape[1] >= a.M
         a.out_t, a.ldt, a.nt_begin = out_t.data_ptr(), out_t.stride(0), nt_begin
     if out is None:
-        assert out_t is not None and nt_begin == 0
+        assert attn is not None or (out_t is not None and nt_begin == 0)
         a.out, a.ldo = None, 0
         a.bias = bias.data_ptr() if bias is not None else None
         a.rowbias, a.ld_rowbias, a.rows_per_group, a.res, a.ldres, a.geglu = None, 0, 1, None, 0, 0
@@ -598,6 +605,11 @@ def gemm(
         keep.append(stats_out)
     _fill_colstats(a, colstats_out, keep)
     _fill_split(a, tile, ksplit, ws, stages, operand=out if out is not None else out_t)
+    if attn is not None:
+        assert out is None and a.tile in (0, 4)
+        a.xattn = True  # (a Python attribute, like weight_is_x: gemm_signature marks the class)
+        _launch("mi355x_gemm_attention", (C.byref(a), C.byref(attn[0])), "mi355x_gemm_attention", keep=tuple(keep) + (attn,))
+        return None
     _launch("mi355x_gemm", (C.byref(a),), "mi355x_gemm", keep=tuple(keep))
     return out
 
@@ -717,6 +729,7 @@ def gemm_signature(a: GemmArgs) -> str:
     """Shape class of a GEMM / conv launch: the key of the measured tile table (refiners_amd/engine/tuning.py)."""
     k = sum(int(a.seg[s].k) * (int(a.seg[s].ksize) ** 2 if a.conv else 1) for s in range(a.nseg))
     flags = ("geglu" if a.geglu == 1 else "") + ("T%d" % a.nt_begin if a.out_t else "") + ("ln" if a.ln_stats else "") + ("st" if a.stats_out else "") + ("lora" if a.lora_b else "")
+    flags += "xa" if getattr(a, "xattn", False) else ""  # the launch is mi355x_gemm_attention: a cross-attention rides in it
     return f"{'conv' if a.conv else 'gemm'}:{'f32' if a.dtype == 0 else 'bf16'}:{a.M}x{a.N}x{k}:s{a.nseg}:{flags}"
 
 
@@ -841,13 +854,22 @@ def attention(
     scale: Optional[float] = None,
 ) -> Tensor:
     """q, out: [B, Lq, H*D] views (last dim contiguous). streams: (k [B, Lk(+), H*D] view, vt [H*D, B, Lkp] view, Lk, out_scale)."""
+    a, _ = attention_args(q, out, num_heads, streams, scale)
+    _launch("mi355x_attention", (C.byref(a),), "mi355x_attention")
+    return out
+
+
+def attention_args(q: Optional[Tensor], out: Tensor, num_heads: int, streams: Sequence[tuple[Tensor, Tensor, int, float]], scale: Optional[float] = None) -> tuple:
+    """(AttnArgs, the tensors it points to) of mi355x_attention; q = None for gemm(..., attn=): the Q projection's launch produces the queries itself."""
     a = AttnArgs()
-    B, Lq, HD = q.shape
+    B, Lq, HD = out.shape
     D = HD // num_heads
-    a.dtype = dtype_code(q.dtype)
+    a.dtype = dtype_code(out.dtype)
     a.B, a.H, a.D, a.Lq, a.nstream = B, num_heads, D, Lq, len(streams)
-    assert q.stride(2) == 1 and out.stride(2) == 1
-    a.q, a.ldq, a.q_batch_stride = q.data_ptr(), q.stride(1), q.stride(0)
+    assert out.stride(2) == 1
+    if q is not None:
+        assert q.stride(2) == 1 and tuple(q.shape) == (B, Lq, HD)
+        a.q, a.ldq, a.q_batch_stride = q.data_ptr(), q.stride(1), q.stride(0)
     a.out, a.ldo, a.o_batch_stride = out.data_ptr(), out.stride(1), out.stride(0)
     a.scale = scale if scale is not None else D ** -0.5
     for s, (k, vt, Lk, osc) in enumerate(streams):
@@ -856,8 +878,18 @@ def attention(
         kv.k, kv.ldk, kv.k_batch_stride = k.data_ptr(), k.stride(1), k.stride(0)
         kv.vt, kv.ldvt, kv.vt_batch_stride = vt.data_ptr(), vt.stride(0), vt.stride(1)
         kv.Lk, kv.out_scale = Lk, osc
-    _launch("mi355x_attention", (C.byref(a),), "mi355x_attention")
-    return out
+    return a, (q, out, tuple(streams))
+
+
+def xattn_tile_ok(M: int, N: int, K: int, dtype: torch.dtype, ln: bool, lora: bool) -> bool:
+    """Would mi355x_gemm run this one-segment GEMM on the 64 x 64 tile of the 4-wave loop, the only tile with a cross-attention form?  The measured table's
+    entry for the shape class, else the library's heuristic (gemm_kernel.cuh pick_tile: at most 256 tiles of 128 x 128)."""
+    from .engine import tuning
+
+    tile, _ = tuning.lookup(f"gemm:{'f32' if dtype == torch.float32 else 'bf16'}:{M}x{N}x{K}:s1:{'ln' if ln else ''}{'lora' if lora else ''}", 0)
+    if os.environ.get("REFINERS_AMD_FORCE_TILE"):
+        tile = int(os.environ["REFINERS_AMD_FORCE_TILE"])
+    return tile == 4 or (tile == 0 and ((M + 127) // 128) * ((N + 127) // 128) <= 256)
 
 
 def attention_general(
