@@ -410,7 +410,8 @@ int mi355x_softmax_rows(int32_t dtype, const float* s, int64_t lds, void* out, i
  *   accumulate = 1 and scale = 1 / heads, giving attn_map.mean(dim=1).sum(dim=1) of SAGAdapter.compute_sag_mask (:72-84).
  * mi355x_sag_degrade: compute_degraded_latents (:86-95) in one kernel: x0 = (x - coef[2]*eps) / coef[1] (Solver.remove_noise), k x k
  *   Gaussian blur with reflect padding (separable weights w1[ksize], fluxion/utils.py:65-113) where mass[b][cell] > 1 (cell = the
- *   nearest-neighbour (ah, aw) attention cell of the pixel), then coef[1] * (.) + coef[2] * eps (Solver.add_noise).
+ *   nearest-neighbour (ah, aw) attention cell of the pixel by torch's `nearest` rule: min(floor(dst * (float(ah) / float(h))), ah - 1) per
+ *   axis, in float32), then coef[1] * (.) + coef[2] * eps (Solver.add_noise).
  *   x, eps, out: [n][C][h][w] contiguous; mass: float32 [n][ah*aw]; coef: device floats, the step's row of the CFG+DDIM table. */
 int mi355x_colsum_rows(int32_t dtype, const void* p, int64_t ldp, int32_t M, int32_t L, float* acc, int32_t accumulate, float scale, void* stream);
 int mi355x_sag_degrade(int32_t dtype, const void* x, const void* eps, const float* mass, int32_t ah, int32_t aw, const float* coef, const float* w1,

@@ -306,7 +306,9 @@ __global__ __launch_bounds__(256) void colsum_rows_kernel(const T* __restrict__ 
 // Self-Attention Guidance, latent side (SAGAdapter.compute_degraded_latents, self_attention_guidance.py:62-95) in one pass:
 //   x0   = (x - noise_std * eps) / scale_factor                      solver.remove_noise
 //   blur = gaussian_blur(x0, k x k, reflect padding)                 separable weights w1[k] from the host
-//   m    = mass[b][nearest (ah, aw) cell of the pixel] > 1           compute_sag_mask + nearest interpolate
+//   m    = mass[b][nearest (ah, aw) cell of the pixel] > 1           compute_sag_mask + nearest interpolate: torch's rule, the cell of row
+//                                                                    py is min(floor(py * (float(ah) / float(h))), ah - 1) in float32 (not py * ah / h
+//                                                                    in integers, which differs at e.g. h = 122, ah = 16, row 61)
 //   out  = scale_factor * (m ? blur : x0) + noise_std * eps          solver.add_noise
 // x, eps, out: [n][C][h][w]; coef[1] = scale factor, coef[2] = noise std of the step (the CFG+DDIM kernel's device table row).
 template <typename T>
@@ -316,6 +318,7 @@ __global__ __launch_bounds__(256) void sag_degrade_kernel(const T* __restrict__ 
     const int64_t total = (int64_t)n * C * h * w;
     const float a = coef[1], sd = coef[2];
     const int half = ks / 2;
+    const float sy = (float)ah / (float)h, sx = (float)aw / (float)w;  // torch's nearest: min(floor(dst * scale), size - 1) in float32
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int px = (int)(i % w), py = (int)((i / w) % h);
         const int64_t plane = i / ((int64_t)h * w);  // b * C + c
@@ -324,7 +327,7 @@ __global__ __launch_bounds__(256) void sag_degrade_kernel(const T* __restrict__ 
         const T* ep = eps + plane * h * w;
         const float e0 = to_f32(ep[py * w + px]);
         const float x0 = (to_f32(xp[py * w + px]) - sd * e0) / a;
-        const int cy = (int)(((int64_t)py * ah) / h), cx = (int)(((int64_t)px * aw) / w);
+        const int cy = min((int)floorf((float)py * sy), ah - 1), cx = min((int)floorf((float)px * sx), aw - 1);
         float v = x0;
         if (mass[(int64_t)b * ah * aw + cy * aw + cx] > 1.0f) {
             float acc = 0.f;
