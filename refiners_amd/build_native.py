@@ -13,8 +13,8 @@ from pathlib import Path
 
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = CSRC / "libmi355x_refiners.so"
-SOURCES = ["gemm.hip", "gemm_conv.hip", "gemm_xattn.hip", "gemm8.hip", "attention.hip", "attention_general.hip", "norm.hip", "elementwise.hip", "sam_decoder.hip", "sam_hq.hip", "window_attention.hip", "mvanet.hip", "dinov2.hip", "ella.hip", "lineart.hip", "reference_only.hip", "style_aligned.hip", "multi_diffusion.hip", "tiled_vae.hip", "solver_step.hip", "cond_input.hip"]
-HEADERS = ["common.cuh", "attn_short_body.cuh", "gemm_params.cuh", "gemm_epilogue.cuh", "gemm_kernel.cuh", "gemm8_kernel.cuh", "gemm_lora_producer.cuh", "gemm_tiles.cuh", "sam_mask_head.cuh", "solver_update.cuh", "../../include/mi355x_refiners.h", "../../include/mi355x_refiners_sam_hq.h", "../../include/mi355x_refiners_solver_step.h", "../../include/mi355x_refiners_swin.h", "../../include/mi355x_refiners_mvanet.h", "../../include/mi355x_refiners_dinov2.h", "../../include/mi355x_refiners_ella.h", "../../include/mi355x_refiners_lineart.h", "../../include/mi355x_refiners_reference_only.h", "../../include/mi355x_refiners_cond_input.h", "../../include/mi355x_refiners_xattn.h"]
+SOURCES = ["gemm.hip", "gemm_conv.hip", "gemm_xattn.hip", "gemm8.hip", "attention.hip", "attention_general.hip", "norm.hip", "elementwise.hip", "sam_decoder.hip", "sam_hq.hip", "window_attention.hip", "mvanet.hip", "dinov2.hip", "ella.hip", "lineart.hip", "reference_only.hip", "style_aligned.hip", "multi_diffusion.hip", "tiled_vae.hip", "solver_step.hip", "cond_input.hip", "sde_step.hip"]
+HEADERS = ["common.cuh", "attn_short_body.cuh", "gemm_params.cuh", "gemm_epilogue.cuh", "gemm_kernel.cuh", "gemm8_kernel.cuh", "gemm_lora_producer.cuh", "gemm_tiles.cuh", "sam_mask_head.cuh", "solver_update.cuh", "../../include/mi355x_refiners.h", "../../include/mi355x_refiners_sam_hq.h", "../../include/mi355x_refiners_solver_step.h", "../../include/mi355x_refiners_swin.h", "../../include/mi355x_refiners_mvanet.h", "../../include/mi355x_refiners_dinov2.h", "../../include/mi355x_refiners_ella.h", "../../include/mi355x_refiners_lineart.h", "../../include/mi355x_refiners_reference_only.h", "../../include/mi355x_refiners_cond_input.h", "../../include/mi355x_refiners_xattn.h", "../../include/mi355x_refiners_sde_step.h"]
 ARCH = "gfx950"
 #: headers each translation unit includes (an incremental build -- `python -m refiners_amd.build_native` without --force -- recompiles a source only when it or one of these changed)
 DEPS = {
@@ -32,6 +32,7 @@ DEPS = {
     "lineart.hip": ["common.cuh", "../../include/mi355x_refiners_lineart.h"],
     "reference_only.hip": ["common.cuh", "../../include/mi355x_refiners_reference_only.h"],
     "cond_input.hip": ["common.cuh", "solver_update.cuh", "../../include/mi355x_refiners_cond_input.h"],
+    "sde_step.hip": ["common.cuh", "solver_update.cuh", "../../include/mi355x_refiners_sde_step.h"],
 }
 
 

@@ -27,3 +27,11 @@ template <typename T> MI_DEV float linear_update(float xv, float eps, float hv, 
         d = hx * xv + he * eps;
     return fmaf(kp, hv, fmaf(kd, d, fmaf(kx, xv, ke * eps)));
 }
+
+// The same with a fifth operand, the step's Gaussian draw (SDE DPM-Solver++ 2M, solvers/dpm.py:241-246, 284-290): x' = linear_update + kn noise.
+// Exactly one more fused multiply-add around the list above, so kn = 0 gives what linear_update gives (sde_step.hip, both of its forms).
+template <typename T>
+MI_DEV float sde_update(float xv, float eps, float hv, float nz, float hx, float he, float kx, float ke, float kd, float kp, float kn, float& d) {
+#pragma clang fp contract(off)
+    return fmaf(kn, nz, linear_update<T>(xv, eps, hv, hx, he, kx, ke, kd, kp, d));
+}

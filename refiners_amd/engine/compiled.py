@@ -397,6 +397,8 @@ class CompiledSDXL:
     refiners_amd.latent_diffusion.solvers (anything with `linear_step`): guidance + update + the next step's model-input
     scaling then run as ONE kernel (mi355x_cfg_linear_step) and the two cat(x, x) copies disappear from the step.
     SD1.5 UNets work too: leave `pooled_text_embedding` / `time_ids` out of `set_inputs`.
+    A stochastic `DPMSolver` (`sde_variance=1.0`) ends its step in mi355x_cfg_sde_step / mi355x_sde_step, the same update with the step's Gaussian
+    draw as a fifth operand.  The draw is made per step BEFORE the graph is replayed, from `set_inputs`' generator, into a buffer the graph reads.
 
     `classifier_free_guidance=False` (the reference's `sdxl.classifier_free_guidance = False`, model.py:128-159: LCM, LCM-LoRA, SDXL-Lightning):
     the UNet runs on x alone -- embeddings of n rows, a program lowered for (n, C, H, W) -- and the update is mi355x_ddim_step /
@@ -440,6 +442,7 @@ class CompiledSDXL:
         # stable address, [1 or n, E, h, w]; the UNet then reads (2n or n, 4 + E, h, w) and x stays (n, 4, h, w)
         self.cond: Optional[Tensor] = None
         self.in_scale: Optional[Tensor] = None  # one float32 on the device: the solver's input scale of the step that primes the model input
+        self.sde_noise: Optional[Tensor] = None
 
     @property
     def condition_scale(self) -> float:
@@ -470,23 +473,34 @@ class CompiledSDXL:
     def solver(self, value: Any) -> None:
         self._solver = value
         self.linear = hasattr(value, "linear_step")
+        # SDE DPM-Solver++: nine-column rows, the draw in a buffer of its own (LCM's `needs_noise` lends it the history slot; this update keeps its history)
+        self.sde = self.linear and float(getattr(value, "sde_variance", 0.0) or 0.0) != 0.0
         self.coef_table, self.graph = None, None  # other coefficients, possibly another update kernel
 
     def _tables(self, device: torch.device) -> None:
         rows = []
-        for s in range(self.solver.num_inference_steps):
+        # a DDIM whose `timesteps` were replaced (Restart sampling: fewer timesteps than num_inference_steps) takes len(timesteps) - 1 steps, each
+        # towards the next timestep; `coefficients` compares the step with num_inference_steps as the reference does
+        steps = self.solver.num_inference_steps
+        if not self.linear and len(self.solver.timesteps) != steps:
+            steps = len(self.solver.timesteps) - 1
+        for s in range(steps):
             if self.linear:
                 rows.append([self.condition_scale, *self.solver.linear_step(s)])
             else:
                 cur, sig, prev, nf = self.solver.coefficients(s)
                 rows.append([self.condition_scale, cur, sig, prev, nf, 0.0, 0.0, 0.0])
         self.coef_table = torch.tensor(rows, dtype=torch.float32, device=device)
-        self.coef = torch.zeros(8, dtype=torch.float32, device=device)
+        self.coef = torch.zeros(self.coef_table.shape[1], dtype=torch.float32, device=device)  # (nine floats for the SDE form; the other kernels read eight)
         # a solver whose input scale is 1 at every step (DDIM, DPM-Solver++, LCM) leaves the constant input channels as priming wrote them; Euler's
         # are rescaled by every step's last launch (mi355x_cond_step with the constants given)
         self.scales_input = self.linear and any(float(self.solver.input_scale(s)) != 1.0 for s in range(self.solver.num_inference_steps))
         self.in_scale = torch.ones(1, dtype=torch.float32, device=device)
         self.ts_table = self.solver.timesteps.to(device=device, dtype=torch.float32)
+        if 0 < steps < self.solver.num_inference_steps and self.ts_table.numel() < self.solver.num_inference_steps:
+            # (a Restart segment: padded to the trajectory's length, which is what sizes the lowered program's timestep-embedding table --
+            # the segment then runs on the caller's program and buffers, and the caller's captured graph stays valid)
+            self.ts_table = torch.cat((self.ts_table, self.ts_table[-1:].expand(self.solver.num_inference_steps - self.ts_table.numel())))
         # Self-Attention Guidance degrades the latents through Solver.remove_noise / add_noise: (-, scale_t, std_t) per step, for mi355x_sag_degrade.
         # A solver whose add_noise / remove_noise the reference itself cannot evaluate (Euler: float timesteps) has no table; SAG then raises.
         # The one refusal that is the reference's own: a solver whose timesteps are floats (Euler) cannot index the integer train-time tables
@@ -497,7 +511,7 @@ class CompiledSDXL:
             self.sag_table = None
         else:
             try:
-                self.sag_table = torch.tensor([[0.0, *self.solver.sag_coefficients(s)] for s in range(self.solver.num_inference_steps)], dtype=torch.float32, device=device)
+                self.sag_table = torch.tensor([[0.0, *self.solver.sag_coefficients(s)] for s in range(steps)], dtype=torch.float32, device=device)
             except IndexError:  # the mirror's Euler refuses for every spacing (its trailing timesteps are integers, but that combination has no golden yet)
                 self.sag_table = None
         self.sag_coef = torch.zeros(3, dtype=torch.float32, device=device)
@@ -538,6 +552,7 @@ class CompiledSDXL:
             # the solver history lives as long as x does: a captured graph holds both addresses, so neither may be
             # re-allocated per trajectory (a fresh zeros_like() here left the graph reading / writing a freed block)
             self.hist = torch.zeros_like(self.x)
+            self.sde_noise = torch.zeros_like(self.x)  # the per-step draw of a stochastic solver (and Restart's): the same lifetime, for the same reason
             self.graph = None
         self.x.copy_(x)
         if input_condition is None:
@@ -724,6 +739,8 @@ class CompiledSDXL:
         """The step's last launch: (guidance +) solver update + history + the next step's model input."""
         if self.cond is not None:
             native.cond_step(self.x, io.out, self.hist, io.x, self.cond if self.scales_input else None, self.coef, self.linear, self._cfg)
+        elif self.sde:
+            (native.cfg_sde_step if self._cfg else native.sde_step)(self.x, io.out, self.hist, self.sde_noise, io.x, self.coef)
         elif self._cfg:
             native.cfg_linear_step(self.x, io.out, self.hist, io.x, self.coef)
         elif self.linear:
@@ -740,6 +757,9 @@ class CompiledSDXL:
         if self.coef_table is None or self.coef_table.device != self.x.device:
             self._tables(self.x.device)  # condition_scale / solver changed since the last call
         eng = self.engine
+        if self.sde:  # combinations without a golden are not lowered (the precedent in latent_diffusion/solvers.py)
+            assert self.cond is None, "a stochastic DPMSolver (sde_variance=1.0) with input_condition is not lowered: mi355x_cond_step has no noise operand"
+            assert not self._cfg or self._sag_adapter() is None, "a stochastic DPMSolver (sde_variance=1.0) with Self-Attention Guidance is not lowered"
         got = dict(self.inputs, timestep=self.ts_table[step : step + 1], timesteps_all=self.ts_table, step_index=step)
         if eng.reference_only():  # the guide is noised per step by the caller (ReferenceOnlyControlAdapter.set_controlnet_condition): read on every call
             got["guide"] = eng._contexts().get("reference_only_control", {}).get("guide")
@@ -833,6 +853,9 @@ class CompiledSDXL:
             self.hist.copy_(noise)
         s0 = float(self.solver.input_scale(step))
         y = unet(xin * s0 if s0 != 1.0 else xin).contiguous()
+        if self.sde:
+            (native.cfg_sde_step if self._cfg else native.sde_step)(x, y, self.hist, self._draw(getattr(self, "generator", None)), None, self.coef)
+            return x
         (native.cfg_linear_step if self._cfg else native.linear_step)(x, y, self.hist, None, self.coef)  # (no model-input buffer: the next step scales its input itself)
         return x
 
@@ -924,6 +947,8 @@ class CompiledSDXL:
             sdt = getattr(self.solver, "dtype", self.x.dtype)
             noise = torch.randn(tuple(self.x.shape), generator=getattr(self, "generator", None), device=sdev, dtype=sdt)
             self.hist.copy_(noise)
+        if self.sde:
+            self._draw(getattr(self, "generator", None))
         if not self.primed or self.primed_key != gkey:  # first step of a trajectory, or the engine re-lowered into new buffers
             s0 = float(self.solver.input_scale(step)) if self.linear else 1.0  # (DDIM does not scale its model input)
             if self.cond is not None:
@@ -948,6 +973,56 @@ class CompiledSDXL:
                 self._update(io)
             self.graph, self.graph_key = g, gkey
         self.graph.replay()
+        return self.x
+
+    def _draw(self, generator: Optional[torch.Generator]) -> Tensor:
+        """One Gaussian draw of the latents' shape and dtype into `sde_noise`, outside any captured graph: a CPU generator cannot be captured at
+        all, and a device generator would have to be registered with the graph before capture, while it changes with every set_inputs.  Drawn
+        as the reference draws it (dpm.py:317-322: torch.randn of x's shape and dtype) on the generator's device -- a CPU generator draws on the
+        CPU and the numbers are copied over, so a trajectory recorded on the CPU can be followed draw for draw -- or on the latents' device from
+        the global stream without one."""
+        x, buf = self.x, self.sde_noise
+        assert x is not None and buf is not None
+        dev = generator.device if generator is not None else x.device
+        buf.copy_(torch.randn(tuple(x.shape), generator=generator, device=dev, dtype=x.dtype))
+        return buf
+
+    @torch.no_grad()
+    def restart(self, restart: Any, generator: Optional[torch.Generator] = None) -> Tensor:
+        """Restart sampling (latent_diffusion/restart.py:47-77) on the resident latents with the staged inputs: `restart` is anything with
+        `timesteps` (descending train timesteps of the interval) and `num_iterations`, e.g. refiners_amd.latent_diffusion.restart.Restart.
+        Per iteration: one draw, x <- factor x + sqrt(1 - factor^2) noise with factor = scale[t_first] / scale[t_last] (add_noise_interval), the
+        model input primed again, then the DDIM segment under a temporary DDIM that carries those timesteps.  The caller's solver, coefficient
+        tables and captured graph are put back afterwards."""
+        from ..latent_diffusion.sampling import DDIM
+
+        assert self.x is not None and self.sde_noise is not None, "call set_inputs first"
+        assert isinstance(self.solver, DDIM), "Restart sampling only works with DDIM solver"
+        ts = restart.timesteps.cpu()
+        assert ts.numel() >= 2, "a restart interval needs two timesteps at least"
+        tables = ("coef_table", "coef", "scales_input", "in_scale", "ts_table", "sag_table", "sag_coef")
+        saved = (self._solver, {k: getattr(self, k, None) for k in tables}, self.graph, self.graph_key)
+        programs = [(e, None if e is None else e.io) for e in (self.engine, self.engine_c)]
+        inner = DDIM(self.solver.num_inference_steps)
+        inner.timesteps = ts
+        csf = inner.cumulative_scale_factors  # (float32, as the reference's solver computes the factor)
+        factor = csf[int(ts[0])] / csf[int(ts[-1])]
+        alpha, beta = float(factor), float(torch.sqrt(1 - factor ** 2))
+        self.solver = inner  # (drops the table and the graph: rebuilt for the segment)
+        try:
+            for _ in range(int(restart.num_iterations)):
+                native.axpby(self.x, alpha, self._draw(generator), beta, self.x)
+                self.primed = False
+                for s in range(ts.numel() - 1):
+                    self.step(s)
+        finally:
+            self._solver, self.linear, self.sde = saved[0], hasattr(saved[0], "linear_step"), False
+            for k, v in saved[1].items():
+                setattr(self, k, v)
+            # the caller's graph holds the programs' buffers by address: it comes back only if the segment ran on the same ones
+            same = all(e is None or e.io is io for e, io in programs)
+            self.graph, self.graph_key = (saved[2], saved[3]) if same else (None, None)
+            self.primed = False
         return self.x
 
     @torch.no_grad()

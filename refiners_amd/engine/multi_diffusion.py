@@ -55,6 +55,8 @@ def solver_tables(solver: Any, cache: Optional[dict] = None) -> Any:
     and schedule.  A solver that draws noise per step is refused: its update is not a function of (x, eps, history)."""
     if getattr(solver, "needs_noise", None) is not None or type(solver).__name__ == "LCMSolver":
         raise Unsupported(f"{type(solver).__name__} draws noise per step")
+    if hasattr(solver, "linear_step") and float(getattr(solver, "sde_variance", 0.0) or 0.0) != 0.0:  # the mirror's SDE DPM-Solver++ (it has no needs_noise)
+        raise Unsupported(f"{type(solver).__name__} with an SDE variance draws noise per step")
     if hasattr(solver, "coefficients") or hasattr(solver, "linear_step"):
         return solver
     cache = cache if cache is not None else {}
@@ -74,7 +76,8 @@ def solver_tables(solver: Any, cache: Optional[dict] = None) -> Any:
             raise Unsupported("DPMSolver with an SDE variance draws noise per step")
         spacing = str(getattr(getattr(params, "timesteps_spacing", None), "value", "custom")).lower()
         mine = solvers.DPMSolver(n, first_inference_step=first, last_step_first_order=bool(getattr(solver, "last_step_first_order", False)),
-                                 timesteps_spacing=spacing if spacing in ("custom", "trailing") else "custom")
+                                 timesteps_spacing=spacing if spacing in ("custom", "trailing") else "custom",
+                                 sigma_schedule=getattr(getattr(params, "sigma_schedule", None), "value", getattr(params, "sigma_schedule", None)))
     else:
         raise Unsupported(f"solver {name} has no table form here")
     if not torch.equal(mine.timesteps.cpu().double(), solver.timesteps.cpu().double()):

@@ -1,7 +1,7 @@
-"""Host-side mirror of refiners' other deterministic solvers -- SURVEY.md section 8(f) next-4:
+"""Host-side mirror of refiners' other solvers -- SURVEY.md section 8(f) next-4:
 
 * `Euler`      `latent_diffusion/solvers/euler.py:13-100`  (k-diffusion Euler, noise prediction; scales the model input)
-* `DPMSolver`  `latent_diffusion/solvers/dpm.py:36-329`    (DPM-Solver++ 2M, `sde_variance = 0`; SD1.5's default solver)
+* `DPMSolver`  `latent_diffusion/solvers/dpm.py:36-329`    (DPM-Solver++ 2M, ODE and SDE form, every sigma schedule; SD1.5's default solver)
 * `LCMSolver`  `latent_diffusion/solvers/lcm.py:15-150`    (consistency jump + re-noising to an emulated DPM schedule; stochastic)
 
 on the reference's default schedule (`solvers/solver.py:96-123, 386-416`: 1000 train steps, quadratic betas
@@ -13,6 +13,9 @@ on the reference's default schedule (`solvers/solver.py:96-123, 386-416`: 1000 t
     d    = hx * x + he * eps                       the quantity the solver keeps (DPM++: the data estimate x0; Euler: eps)
     x'   = kx * x + ke * eps + kd * d + kp * hist  the update
     hist = d ;  model input of the next step = s_next * x'
+
+The SDE form of DPM-Solver++ (`sde_variance=1.0`) adds the step's Gaussian draw as a fifth operand, x' += kn * noise: its `linear_step` row has
+one more float and the step ends in `mi355x_cfg_sde_step` / `mi355x_sde_step`.  `refiners_amd.latent_diffusion.restart` mirrors Restart sampling.
 
 `__call__` is the unfused torch path with the reference's own formulas and operation order.
 """
@@ -129,15 +132,28 @@ class Euler(_Schedule):
 
 
 class DPMSolver(_Schedule):
-    """DPM-Solver++ (2M), deterministic: first-order update on the first (and optionally last) step, second-order
+    """DPM-Solver++ (2M): first-order update on the first (and optionally last) step, second-order
     multistep otherwise; CUSTOM timestep spacing, sigmas interpolated at the timesteps with sigma_min appended, constants
-    computed in float64 (dpm.py:58-120, 224-329)."""
+    computed in float64 (dpm.py:58-120, 224-329).
+
+    `sigma_schedule` ("uniform" | "quadratic" | "karras": SolverParams.sigma_schedule, dpm.py:125-146) spaces the sigmas themselves,
+    rho = 1 / 2 / 7, instead of interpolating them at the spaced timesteps.  `sde_variance=1.0` (SolverParams.sde_variance) is the SDE
+    form: one Gaussian draw per step (dpm.py:241-246, 284-290).  `sde_variance` is an instance attribute, and what marks the stochastic form:
+    the class has no `needs_noise`, which means "the draw goes into the history slot" (LCMSolver) -- this update keeps its history."""
+
+    SIGMA_SCHEDULES = {"uniform": 1, "quadratic": 2, "karras": 7}
 
     def __init__(self, num_inference_steps: int, first_inference_step: int = 0, last_step_first_order: bool = False, device: Any = "cpu",
                  dtype: torch.dtype = torch.float32, num_train_timesteps: int = 1000, initial_diffusion_rate: float = 8.5e-4,
-                 final_diffusion_rate: float = 1.2e-2, timesteps_spacing: str = "custom") -> None:
+                 final_diffusion_rate: float = 1.2e-2, timesteps_spacing: str = "custom", sigma_schedule: str | None = None,
+                 sde_variance: float = 0.0) -> None:
         super().__init__(num_inference_steps, first_inference_step, num_train_timesteps, initial_diffusion_rate, final_diffusion_rate)
         assert timesteps_spacing in ("custom", "trailing")
+        sigma_schedule = getattr(sigma_schedule, "value", sigma_schedule)  # (refiners' NoiseSchedule is a str enum)
+        assert sigma_schedule is None or sigma_schedule in self.SIGMA_SCHEDULES, sigma_schedule
+        if sde_variance not in (0.0, 1.0):
+            raise NotImplementedError("DPMSolver only supports sde_variance=0.0 or 1.0")
+        self.sigma_schedule, self.sde_variance = sigma_schedule, float(sde_variance)
         self.last_step_first_order = last_step_first_order
         # (the reference builds the train-time schedule in float32 and only then switches to float64: dpm.py:74-81)
         csf, nstd = self.cumulative_scale_factors.double(), self.noise_std.double()
@@ -146,7 +162,15 @@ class DPMSolver(_Schedule):
         else:  # TRAILING (solver.py:229-232): what LCMSolver asks of the DPM solver it emulates
             spaced = torch.arange(num_train_timesteps - 1, 0, -(num_train_timesteps // num_inference_steps))
         sigmas_all = nstd / csf
-        sig = torch.tensor(np.interp(spaced.numpy(), np.arange(0, len(sigmas_all)), sigmas_all.numpy()))
+        if sigma_schedule is None:
+            sig = torch.tensor(np.interp(spaced.numpy(), np.arange(0, len(sigmas_all)), sigmas_all.numpy()))
+        else:
+            # dpm.py:140-146, with the reference's dtypes: a float32 linspace combined with 0-dim float64 sigmas stays float32, so the rescaled
+            # sigmas are float32 VALUES (widened by the cat below)
+            rho = self.SIGMA_SCHEDULES[sigma_schedule]
+            lin = torch.linspace(0, 1, steps=num_inference_steps)
+            first, last = sigmas_all[0], sigmas_all[-1]
+            sig = ((first ** (1 / rho) + lin * (last ** (1 / rho) - first ** (1 / rho))) ** rho).flip(0)
         self.sigmas = torch.cat([sig, sigmas_all[0:1]])
         self.cumulative_scale_factors = 1 / torch.sqrt(self.sigmas ** 2 + 1)
         self.noise_std = self.sigmas * self.cumulative_scale_factors
@@ -181,17 +205,41 @@ class DPMSolver(_Schedule):
     def _first_order(self, step: int) -> bool:
         return step == self.first_inference_step or (self.last_step_first_order and step == self.num_inference_steps - 1)
 
+    @property
+    def stochastic(self) -> bool:
+        return self.sde_variance != 0.0
+
+    @staticmethod
+    def _inverse_ratio(lam: list, step: int) -> float:
+        """1 / r of the second-order update, r = (lam[s] - lam[s-1]) / (lam[s+1] - lam[s]).  A sigma schedule ends on two sigmas that coincide
+        to float32 precision (the rescaled first sigma IS sigma_min): the reference's tensor arithmetic divides by r = x / 0 = inf there, or
+        by an r of 1e6 and more beside a factor 1 - exp(delta) of 1e-6 and less -- a term below 1e-12 of the update.  Both are 0 here."""
+        den = lam[step + 1] - lam[step]
+        return 0.0 if abs(den) < 1e-6 else den / (lam[step] - lam[step - 1])
+
     def linear_step(self, step: int) -> tuple[float, ...]:
-        """(hx, he, kx, ke, kd, kp, s_next) with d = x0 = (x - noise_std * eps) / scale, hist = the previous step's x0."""
+        """(hx, he, kx, ke, kd, kp, s_next) with d = x0 = (x - noise_std * eps) / scale, hist = the previous step's x0.
+        The SDE form returns one more float, (..., s_next, kn): the coefficient of the step's Gaussian draw."""
         a, n, lam = (t.tolist() for t in self._tables64)
         hx, he = 1.0 / a[step], -n[step] / a[step]
         delta = lam[step] - lam[step + 1]
+        if self.stochastic:  # dpm.py:241-246, 284-290
+            f = 1.0 - float(np.exp(2.0 * delta))
+            kx = n[step + 1] / n[step] * float(np.exp(delta))
+            kn = n[step + 1] * max(f, 0.0) ** 0.5
+            if self._first_order(step):
+                return (hx, he, kx, 0.0, a[step + 1] * f, 0.0, 1.0, kn)
+            half = 0.5 * a[step + 1] * f * self._inverse_ratio(lam, step)
+            return (hx, he, kx, 0.0, a[step + 1] * f + half, -half, 1.0, kn)
         f = 1.0 - float(np.exp(delta))
         kx = n[step + 1] / n[step]
         if self._first_order(step):
             return (hx, he, kx, 0.0, f * a[step + 1], 0.0, 1.0)
-        r = (lam[step] - lam[step - 1]) / (lam[step + 1] - lam[step])
-        half = 0.5 * a[step + 1] * f / r
+        if self.sigma_schedule is None:
+            r = (lam[step] - lam[step - 1]) / (lam[step + 1] - lam[step])
+            half = 0.5 * a[step + 1] * f / r
+        else:
+            half = 0.5 * a[step + 1] * f * self._inverse_ratio(lam, step)
         return (hx, he, kx, 0.0, a[step + 1] * f + half, -half, 1.0)
 
     def __call__(self, x: Tensor, predicted_noise: Tensor, step: int, generator: Any = None) -> Tensor:
@@ -200,12 +248,21 @@ class DPMSolver(_Schedule):
         self.estimated_data.append(x0)
         lam, a, n = self.signal_to_noise_ratios, self.cumulative_scale_factors, self.noise_std
         delta = lam[step] - lam[step + 1]
+        # (dpm.py:317-322: drawn on every step, before the update, on x's device and in x's dtype)
+        noise = torch.randn(x.shape, generator=generator, device=x.device, dtype=x.dtype) * self.sde_variance if self.stochastic else None
         if self._first_order(step):
-            return (n[step + 1] / n[step]) * x + (1.0 - torch.exp(delta)) * a[step + 1] * x0
+            if noise is None:
+                return (n[step + 1] / n[step]) * x + (1.0 - torch.exp(delta)) * a[step + 1] * x0
+            f = 1.0 - torch.exp(2.0 * delta)
+            return (n[step + 1] / n[step]) * torch.exp(delta) * x + a[step + 1] * f * x0 + n[step + 1] * torch.sqrt(torch.maximum(f, torch.tensor(0))) * noise
         cur, prev = self.estimated_data[-1], self.estimated_data[-2]
         est_delta = (cur - prev) / ((lam[step] - lam[step - 1]) / (lam[step + 1] - lam[step]))
-        f = 1.0 - torch.exp(delta)
-        return (n[step + 1] / n[step]) * x + a[step + 1] * f * cur + 0.5 * a[step + 1] * f * est_delta
+        if noise is None:
+            f = 1.0 - torch.exp(delta)
+            return (n[step + 1] / n[step]) * x + a[step + 1] * f * cur + 0.5 * a[step + 1] * f * est_delta
+        f = 1.0 - torch.exp(2.0 * delta)
+        return ((n[step + 1] / n[step]) * torch.exp(delta) * x + a[step + 1] * f * cur + 0.5 * a[step + 1] * f * est_delta
+                + n[step + 1] * torch.sqrt(torch.maximum(f, torch.tensor(0))) * noise)
 
 
 class LCMSolver(_Schedule):

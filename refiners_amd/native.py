@@ -86,6 +86,8 @@ globals().update({cls.__name__: cls for cls in _abi_reference_only.structs.value
 _abi_cond_input = abi.read({}, abi.HEADER.parent / "mi355x_refiners_cond_input.h")
 #: include/mi355x_refiners_xattn.h, a cross-attention folded into its Q projection (no structs of its own: it takes GemmArgs and AttnArgs)
 _abi_xattn = abi.read({}, abi.HEADER.parent / "mi355x_refiners_xattn.h", base=_abi)
+#: include/mi355x_refiners_sde_step.h, the stochastic solver updates (SDE DPM-Solver++; no structs)
+_abi_sde_step = abi.read({}, abi.HEADER.parent / "mi355x_refiners_sde_step.h")
 _K = _abi.constants
 
 #: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
@@ -110,6 +112,8 @@ EXPORTS_REFERENCE_ONLY = list(_abi_reference_only.functions)
 EXPORTS_COND_INPUT = list(_abi_cond_input.functions)
 #: every symbol include/mi355x_refiners_xattn.h declares
 EXPORTS_XATTN = list(_abi_xattn.functions)
+#: every symbol include/mi355x_refiners_sde_step.h declares
+EXPORTS_SDE_STEP = list(_abi_sde_step.functions)
 #: exported for probing and A/B runs, by design not in the header (no stable contract): name -> (restype, argtypes), applied by load() like the header's
 UNSTABLE = {
     "mi355x_set_option": (C.c_int, [C.c_char_p, C.c_int]),
@@ -205,7 +209,7 @@ def load(path: Optional[Path] = None) -> C.CDLL:
         lib = C.CDLL(str(p))
     except OSError as e:  # e.g. no HIP runtime on this machine
         raise NativeError(f"cannot load {p}: {e}") from e
-    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **_abi_mvanet.functions, **_abi_dinov2.functions, **_abi_ella.functions, **_abi_lineart.functions, **_abi_reference_only.functions, **_abi_cond_input.functions, **_abi_xattn.functions, **UNSTABLE}.items():
+    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **_abi_mvanet.functions, **_abi_dinov2.functions, **_abi_ella.functions, **_abi_lineart.functions, **_abi_reference_only.functions, **_abi_cond_input.functions, **_abi_xattn.functions, **_abi_sde_step.functions, **UNSTABLE}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.mi355x_abi_version() != ABI_VERSION:
@@ -1105,6 +1109,32 @@ def linear_step(x: Tensor, unet_out: Tensor, hist: Tensor, model_in: Optional[Te
     assert coef.dtype == torch.float32 and coef.numel() >= 8 and (model_in is None or (model_in.is_contiguous() and model_in.numel() == x.numel() and model_in.dtype == x.dtype))
     _launch("mi355x_linear_step", (dtype_code(x.dtype), x.data_ptr(), unet_out.data_ptr(), hist.data_ptr(), model_in.data_ptr() if model_in is not None else None,
                                   coef.data_ptr(), x.numel()), "mi355x_linear_step")
+    return x
+
+
+def _sde_step_checks(x: Tensor, unet_out: Tensor, hist: Tensor, noise: Tensor, model_in: Optional[Tensor], coef: Tensor, rows: int) -> None:
+    assert x.is_contiguous() and unet_out.is_contiguous() and hist.is_contiguous() and noise.is_contiguous()
+    assert unet_out.numel() == rows * x.numel() and hist.numel() == x.numel() == noise.numel()
+    assert unet_out.dtype == x.dtype == hist.dtype == noise.dtype
+    assert coef.dtype == torch.float32 and coef.numel() >= 9 and coef.is_cuda
+    assert model_in is None or (model_in.is_contiguous() and model_in.numel() == rows * x.numel() and model_in.dtype == x.dtype and model_in.data_ptr() != x.data_ptr())
+
+
+def cfg_sde_step(x: Tensor, unet_out: Tensor, hist: Tensor, noise: Tensor, model_in: Optional[Tensor], coef: Tensor) -> Tensor:
+    """cfg_linear_step with the step's Gaussian draw as a fifth operand (SDE DPM-Solver++): x, hist [N, ...] in place; noise [N, ...] read only;
+    unet_out [2N, ...]; model_in [2N, ...] or None; coef: 9 float32 on the device = (cfg, hx, he, kx, ke, kd, kp, s_next, kn) -- see
+    mi355x_cfg_sde_step in its header."""
+    _sde_step_checks(x, unet_out, hist, noise, model_in, coef, 2)
+    _launch("mi355x_cfg_sde_step", (dtype_code(x.dtype), x.data_ptr(), unet_out.data_ptr(), hist.data_ptr(), noise.data_ptr(),
+                                   model_in.data_ptr() if model_in is not None else None, coef.data_ptr(), x.numel()), "mi355x_cfg_sde_step", keep=(noise,))
+    return x
+
+
+def sde_step(x: Tensor, unet_out: Tensor, hist: Tensor, noise: Tensor, model_in: Optional[Tensor], coef: Tensor) -> Tensor:
+    """Guidance-free form of cfg_sde_step: unet_out and model_in (or None) have x's n elements; coef[0] is not read -- see mi355x_sde_step."""
+    _sde_step_checks(x, unet_out, hist, noise, model_in, coef, 1)
+    _launch("mi355x_sde_step", (dtype_code(x.dtype), x.data_ptr(), unet_out.data_ptr(), hist.data_ptr(), noise.data_ptr(),
+                               model_in.data_ptr() if model_in is not None else None, coef.data_ptr(), x.numel()), "mi355x_sde_step", keep=(noise,))
     return x
 
 
