@@ -143,3 +143,17 @@ def parse(text: str, names: dict, where: str = "header", base: Optional[Abi] = N
 def read(names: dict, path: Optional[Path] = None, base: Optional[Abi] = None) -> Abi:
     path = Path(path or HEADER)
     return parse(path.read_text(), names, where=path.name, base=base)
+
+
+def read_all(headers: list, include: Path = HEADER.parent) -> dict:
+    """`headers`: rows (key, file name, {C struct: Python class name}), mi355x_refiners.h first -> {key: Abi}; every later header is read
+    with the first as `base`.  A C struct, a Python class or a function that two headers declare raises AbiError with both headers' names:
+    the binding merges what the headers declare, and the later one would silently win."""
+    abis: dict = {}
+    owner: dict = {}
+    for key, fname, names in headers:
+        got = abis[key] = read(names, include / fname, base=next(iter(abis.values()), None))
+        for name in [*got.structs, *(cls.__name__ for cls in got.structs.values()), *got.functions]:
+            if owner.setdefault(name, fname) != fname:
+                raise AbiError(f"{fname}: {name} is already declared by {owner[name]}")
+    return abis

@@ -6,6 +6,7 @@ the GPU box; nothing is installed into site-packages and nothing is JIT-cached u
 from __future__ import annotations
 
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -14,26 +15,25 @@ from pathlib import Path
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = CSRC / "libmi355x_refiners.so"
 SOURCES = ["gemm.hip", "gemm_conv.hip", "gemm_xattn.hip", "gemm8.hip", "attention.hip", "attention_general.hip", "norm.hip", "elementwise.hip", "sam_decoder.hip", "sam_hq.hip", "window_attention.hip", "mvanet.hip", "dinov2.hip", "ella.hip", "lineart.hip", "reference_only.hip", "style_aligned.hip", "multi_diffusion.hip", "tiled_vae.hip", "solver_step.hip", "cond_input.hip", "sde_step.hip"]
-HEADERS = ["common.cuh", "attn_short_body.cuh", "gemm_params.cuh", "gemm_epilogue.cuh", "gemm_kernel.cuh", "gemm8_kernel.cuh", "gemm_lora_producer.cuh", "gemm_tiles.cuh", "sam_mask_head.cuh", "solver_update.cuh", "../../include/mi355x_refiners.h", "../../include/mi355x_refiners_sam_hq.h", "../../include/mi355x_refiners_solver_step.h", "../../include/mi355x_refiners_swin.h", "../../include/mi355x_refiners_mvanet.h", "../../include/mi355x_refiners_dinov2.h", "../../include/mi355x_refiners_ella.h", "../../include/mi355x_refiners_lineart.h", "../../include/mi355x_refiners_reference_only.h", "../../include/mi355x_refiners_cond_input.h", "../../include/mi355x_refiners_xattn.h", "../../include/mi355x_refiners_sde_step.h"]
 ARCH = "gfx950"
+CORE_HEADER = "../../include/mi355x_refiners.h"  # every object depends on it unconditionally, so DEPS leaves it out
+
+
+def _included(path: Path, seen: list[str]) -> list[str]:
+    """Every file `path` reaches through `#include "..."` lines, each resolved against the including file's directory: depth first, in
+    first-seen order, csrc-local headers spelt bare and the others relative to csrc/.  A conditional include counts as unconditional."""
+    for name in re.findall(r'^\s*#\s*include\s*"([^"]+)"', path.read_text(), flags=re.M):
+        inc = (path.parent / name).resolve()
+        spelt = Path(os.path.relpath(inc, CSRC)).as_posix()
+        if spelt not in seen:
+            seen.append(spelt)
+            _included(inc, seen)
+    return seen
+
+
 #: headers each translation unit includes (an incremental build -- `python -m refiners_amd.build_native` without --force -- recompiles a source only when it or one of these changed)
-DEPS = {
-    "gemm.hip": ["common.cuh", "attn_short_body.cuh", "gemm_params.cuh", "gemm_epilogue.cuh", "gemm_kernel.cuh", "gemm8_kernel.cuh", "gemm_lora_producer.cuh", "gemm_tiles.cuh"],
-    "gemm_conv.hip": ["common.cuh", "attn_short_body.cuh", "gemm_params.cuh", "gemm_epilogue.cuh", "gemm_kernel.cuh", "gemm_lora_producer.cuh", "gemm_tiles.cuh"],
-    "gemm_xattn.hip": ["common.cuh", "attn_short_body.cuh", "gemm_params.cuh", "gemm_epilogue.cuh", "gemm_kernel.cuh", "gemm_lora_producer.cuh", "gemm_tiles.cuh", "../../include/mi355x_refiners_xattn.h"],
-    "gemm8.hip": ["common.cuh", "gemm_params.cuh", "gemm_epilogue.cuh", "gemm8_kernel.cuh", "gemm_lora_producer.cuh", "gemm_tiles.cuh"],
-    "attention.hip": ["common.cuh", "attn_short_body.cuh"], "attention_general.hip": ["common.cuh"], "norm.hip": ["common.cuh"], "elementwise.hip": ["common.cuh", "solver_update.cuh"],
-    "sam_decoder.hip": ["common.cuh", "sam_mask_head.cuh"], "sam_hq.hip": ["common.cuh", "sam_mask_head.cuh", "../../include/mi355x_refiners_sam_hq.h"], "style_aligned.hip": ["common.cuh"], "multi_diffusion.hip": ["common.cuh"], "tiled_vae.hip": ["common.cuh"],
-    "solver_step.hip": ["common.cuh", "solver_update.cuh", "../../include/mi355x_refiners_solver_step.h"],
-    "window_attention.hip": ["common.cuh", "../../include/mi355x_refiners_swin.h"],
-    "mvanet.hip": ["common.cuh", "../../include/mi355x_refiners_mvanet.h"],
-    "dinov2.hip": ["common.cuh", "../../include/mi355x_refiners_dinov2.h"],
-    "ella.hip": ["common.cuh", "../../include/mi355x_refiners_ella.h"],
-    "lineart.hip": ["common.cuh", "../../include/mi355x_refiners_lineart.h"],
-    "reference_only.hip": ["common.cuh", "../../include/mi355x_refiners_reference_only.h"],
-    "cond_input.hip": ["common.cuh", "solver_update.cuh", "../../include/mi355x_refiners_cond_input.h"],
-    "sde_step.hip": ["common.cuh", "solver_update.cuh", "../../include/mi355x_refiners_sde_step.h"],
-}
+DEPS = {src: [h for h in _included(CSRC / src, []) if h != CORE_HEADER] for src in SOURCES}
+HEADERS = list(dict.fromkeys([h for src in SOURCES for h in DEPS[src]] + [CORE_HEADER]))
 
 
 def hipcc_path() -> str:
@@ -71,7 +71,7 @@ def build_native(force: bool = False, verbose: bool = False, defines: list[str] 
     for src in SOURCES:
         obj = objdir / (src.replace(".hip", ".o"))
         if not force and not defines and obj.exists():  # incremental: the object is newer than its source and every header it includes
-            deps = [CSRC / src, (CSRC / "../../include/mi355x_refiners.h").resolve(), Path(__file__)] + [CSRC / h for h in DEPS[src]]
+            deps = [CSRC / src, (CSRC / CORE_HEADER).resolve(), Path(__file__)] + [CSRC / h for h in DEPS[src]]
             if all(d.stat().st_mtime <= obj.stat().st_mtime for d in deps):
                 objs.append(obj)
                 continue

@@ -8,6 +8,10 @@ raises `NativeError` (the fused fluxion nodes decide, *before* calling, whether 
 The header is the only description of the ABI: the argument structs (GemmArgs, AttnArgs, ...), the prototypes `load()` sets and the
 scalar constants are read from it at import by refiners_amd.abi, nothing of it is restated here.  What this module adds is the
 Python name of each struct (STRUCT_NAMES), the probing entry points the header leaves out on purpose (UNSTABLE), and the wrappers.
+
+A feature's entry points live in an extension header of their own, include/mi355x_refiners_<feature>.h.  Adding one takes a row in
+ABI_HEADERS here and its source in build_native.SOURCES: the structs, the bound prototypes, the build's dependencies and the header
+tests (tests/test_abi_header_cpu.py) all follow from those two.
 """
 from __future__ import annotations
 
@@ -49,71 +53,32 @@ STRUCT_NAMES = {
     "mi355x_vae_blend_tile": "VaeBlendTile",
     "mi355x_vae_blend_args": "VaeBlendArgs",
 }
-_abi = abi.read(STRUCT_NAMES)
-globals().update({cls.__name__: cls for cls in _abi.structs.values()})  # GemmSeg ... VaeBlendArgs: real ctypes.Structure subclasses
-#: the same for include/mi355x_refiners_sam_hq.h, the HQ-SAM extension of the ABI (mi355x_refiners.h itself is a frozen list)
-SAM_HQ_STRUCT_NAMES = {"mi355x_sam_hq_mask_head_args": "SamHqMaskHeadArgs", "mi355x_sam_mask_head_up_args": "SamMaskHeadUpArgs"}
-_abi_sam_hq = abi.read(SAM_HQ_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_sam_hq.h")
-globals().update({cls.__name__: cls for cls in _abi_sam_hq.structs.values()})
-#: include/mi355x_refiners_solver_step.h, the guidance-free solver updates (no structs)
-_abi_solver_step = abi.read({}, abi.HEADER.parent / "mi355x_refiners_solver_step.h")
-#: include/mi355x_refiners_swin.h, the Swin Transformer's window attention
-SWIN_STRUCT_NAMES = {"mi355x_window_attention_args": "WindowAttentionArgs"}
-_abi_swin = abi.read(SWIN_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_swin.h")
-globals().update({cls.__name__: cls for cls in _abi_swin.structs.values()})
-#: include/mi355x_refiners_mvanet.h, the streaming passes of MVANet's multi-view decoder
-MVANET_STRUCT_NAMES = {"mi355x_mvanet_pool_args": "MvanetPoolArgs", "mi355x_mvanet_gate_args": "MvanetGateArgs", "mi355x_mvanet_resize_add_args": "MvanetResizeAddArgs"}
-_abi_mvanet = abi.read(MVANET_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_mvanet.h")
-globals().update({cls.__name__: cls for cls in _abi_mvanet.structs.values()})
-#: include/mi355x_refiners_dinov2.h, the streaming passes of the DINOv2 encoder
-DINOV2_STRUCT_NAMES = {"mi355x_dinov2_pos_resample_args": "Dinov2PosResampleArgs", "mi355x_dinov2_tokens_args": "Dinov2TokensArgs"}
-_abi_dinov2 = abi.read(DINOV2_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_dinov2.h")
-globals().update({cls.__name__: cls for cls in _abi_dinov2.structs.values()})
-#: include/mi355x_refiners_ella.h, the AdaLayerNorm pass of ELLA's Perceiver resampler
-ELLA_STRUCT_NAMES = {"mi355x_ella_adaln_args": "EllaAdaLnArgs"}
-_abi_ella = abi.read(ELLA_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_ella.h")
-globals().update({cls.__name__: cls for cls in _abi_ella.structs.values()})
-#: include/mi355x_refiners_lineart.h, the stem, InstanceNorm2d passes and head of the InformativeDrawings preprocessor
-LINEART_STRUCT_NAMES = {"mi355x_lineart_stem_args": "LineartStemArgs", "mi355x_lineart_in_stats_args": "LineartInStatsArgs",
-                        "mi355x_lineart_in_apply_args": "LineartInApplyArgs", "mi355x_lineart_head_args": "LineartHeadArgs"}
-_abi_lineart = abi.read(LINEART_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_lineart.h")
-globals().update({cls.__name__: cls for cls in _abi_lineart.structs.values()})
-#: include/mi355x_refiners_reference_only.h, the joint self-attention of reference-only control
-REFERENCE_ONLY_STRUCT_NAMES = {"mi355x_attn_joint_args": "AttnJointArgs"}
-_abi_reference_only = abi.read(REFERENCE_ONLY_STRUCT_NAMES, abi.HEADER.parent / "mi355x_refiners_reference_only.h")
-globals().update({cls.__name__: cls for cls in _abi_reference_only.structs.values()})
-#: include/mi355x_refiners_cond_input.h, step-constant UNet input channels (inpainting, IC-Light; no structs)
-_abi_cond_input = abi.read({}, abi.HEADER.parent / "mi355x_refiners_cond_input.h")
-#: include/mi355x_refiners_xattn.h, a cross-attention folded into its Q projection (no structs of its own: it takes GemmArgs and AttnArgs)
-_abi_xattn = abi.read({}, abi.HEADER.parent / "mi355x_refiners_xattn.h", base=_abi)
-#: include/mi355x_refiners_sde_step.h, the stochastic solver updates (SDE DPM-Solver++; no structs)
-_abi_sde_step = abi.read({}, abi.HEADER.parent / "mi355x_refiners_sde_step.h")
+#: every header of the ABI, mi355x_refiners.h (a frozen list) first: (key, file under include/, {C struct: Python class name})
+ABI_HEADERS = [
+    ("core", "mi355x_refiners.h", STRUCT_NAMES),
+    ("sam_hq", "mi355x_refiners_sam_hq.h", {"mi355x_sam_hq_mask_head_args": "SamHqMaskHeadArgs", "mi355x_sam_mask_head_up_args": "SamMaskHeadUpArgs"}),
+    ("solver_step", "mi355x_refiners_solver_step.h", {}),  # the guidance-free solver updates
+    ("swin", "mi355x_refiners_swin.h", {"mi355x_window_attention_args": "WindowAttentionArgs"}),
+    ("mvanet", "mi355x_refiners_mvanet.h", {"mi355x_mvanet_pool_args": "MvanetPoolArgs", "mi355x_mvanet_gate_args": "MvanetGateArgs", "mi355x_mvanet_resize_add_args": "MvanetResizeAddArgs"}),
+    ("dinov2", "mi355x_refiners_dinov2.h", {"mi355x_dinov2_pos_resample_args": "Dinov2PosResampleArgs", "mi355x_dinov2_tokens_args": "Dinov2TokensArgs"}),
+    ("ella", "mi355x_refiners_ella.h", {"mi355x_ella_adaln_args": "EllaAdaLnArgs"}),  # the AdaLayerNorm pass of ELLA's Perceiver resampler
+    ("lineart", "mi355x_refiners_lineart.h", {"mi355x_lineart_stem_args": "LineartStemArgs", "mi355x_lineart_in_stats_args": "LineartInStatsArgs",
+                                              "mi355x_lineart_in_apply_args": "LineartInApplyArgs", "mi355x_lineart_head_args": "LineartHeadArgs"}),
+    ("reference_only", "mi355x_refiners_reference_only.h", {"mi355x_attn_joint_args": "AttnJointArgs"}),  # the joint self-attention of reference-only control
+    ("cond_input", "mi355x_refiners_cond_input.h", {}),  # step-constant UNet input channels (inpainting, IC-Light)
+    ("xattn", "mi355x_refiners_xattn.h", {}),  # a cross-attention folded into its Q projection: it takes the core header's GemmArgs and AttnArgs
+    ("sde_step", "mi355x_refiners_sde_step.h", {}),  # the stochastic solver updates (SDE DPM-Solver++)
+]
+#: key -> what refiners_amd.abi read from that header (a name that two headers declare is an import error)
+ABIS = abi.read_all(ABI_HEADERS)
+globals().update({cls.__name__: cls for a in ABIS.values() for cls in a.structs.values()})  # GemmSeg ... AttnJointArgs: real ctypes.Structure subclasses
+_abi = ABIS["core"]
 _K = _abi.constants
 
 #: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
 EXPORTS = list(_abi.functions)
-#: every symbol include/mi355x_refiners_sam_hq.h declares
-EXPORTS_SAM_HQ = list(_abi_sam_hq.functions)
-#: every symbol include/mi355x_refiners_solver_step.h declares
-EXPORTS_SOLVER_STEP = list(_abi_solver_step.functions)
-#: every symbol include/mi355x_refiners_swin.h declares
-EXPORTS_SWIN = list(_abi_swin.functions)
-#: every symbol include/mi355x_refiners_mvanet.h declares
-EXPORTS_MVANET = list(_abi_mvanet.functions)
-#: every symbol include/mi355x_refiners_dinov2.h declares
-EXPORTS_DINOV2 = list(_abi_dinov2.functions)
-#: every symbol include/mi355x_refiners_ella.h declares
-EXPORTS_ELLA = list(_abi_ella.functions)
-#: every symbol include/mi355x_refiners_lineart.h declares
-EXPORTS_LINEART = list(_abi_lineart.functions)
-#: every symbol include/mi355x_refiners_reference_only.h declares
-EXPORTS_REFERENCE_ONLY = list(_abi_reference_only.functions)
-#: every symbol include/mi355x_refiners_cond_input.h declares
-EXPORTS_COND_INPUT = list(_abi_cond_input.functions)
-#: every symbol include/mi355x_refiners_xattn.h declares
-EXPORTS_XATTN = list(_abi_xattn.functions)
-#: every symbol include/mi355x_refiners_sde_step.h declares
-EXPORTS_SDE_STEP = list(_abi_sde_step.functions)
+#: every symbol any header declares, in table order: what load() binds and the build checks
+ALL_EXPORTS = [name for a in ABIS.values() for name in a.functions]
 #: exported for probing and A/B runs, by design not in the header (no stable contract): name -> (restype, argtypes), applied by load() like the header's
 UNSTABLE = {
     "mi355x_set_option": (C.c_int, [C.c_char_p, C.c_int]),
@@ -209,7 +174,7 @@ def load(path: Optional[Path] = None) -> C.CDLL:
         lib = C.CDLL(str(p))
     except OSError as e:  # e.g. no HIP runtime on this machine
         raise NativeError(f"cannot load {p}: {e}") from e
-    for name, (restype, argtypes) in {**_abi.functions, **_abi_sam_hq.functions, **_abi_solver_step.functions, **_abi_swin.functions, **_abi_mvanet.functions, **_abi_dinov2.functions, **_abi_ella.functions, **_abi_lineart.functions, **_abi_reference_only.functions, **_abi_cond_input.functions, **_abi_xattn.functions, **_abi_sde_step.functions, **UNSTABLE}.items():
+    for name, (restype, argtypes) in {**{name: sig for a in ABIS.values() for name, sig in a.functions.items()}, **UNSTABLE}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.mi355x_abi_version() != ABI_VERSION:
@@ -1158,7 +1123,7 @@ def cond_step(x: Tensor, unet_out: Tensor, hist: Optional[Tensor], model_in: Ten
     assert x.is_contiguous() and unet_out.is_contiguous() and tuple(unet_out.shape) == (B,) + tuple(x.shape[1:]) and model_in.shape[0] == B
     assert unet_out.dtype == x.dtype == model_in.dtype and coef.dtype == torch.float32 and coef.numel() >= 8
     assert not linear or (hist is not None and hist.is_contiguous() and hist.shape == x.shape and hist.dtype == x.dtype)
-    _launch("mi355x_cond_step", (dtype_code(x.dtype), _abi_cond_input.constants["MI355X_COND_LINEAR" if linear else "MI355X_COND_DDIM"], int(guided), x.data_ptr(),
+    _launch("mi355x_cond_step", (dtype_code(x.dtype), ABIS["cond_input"].constants["MI355X_COND_LINEAR" if linear else "MI355X_COND_DDIM"], int(guided), x.data_ptr(),
                                 unet_out.data_ptr(), hist.data_ptr() if (linear and hist is not None) else None, model_in.data_ptr(),
                                 cond.data_ptr() if cond is not None else None, coef.data_ptr(), n, Cc, E, nc, hw), "mi355x_cond_step", keep=(cond,))
     return x
@@ -1338,7 +1303,7 @@ def window_attention(q: Tensor, k: Tensor, v: Tensor, table: Tensor, out: Tensor
 
 
 # ------------------------------------------------------------------------------------------------ MVANet's decoder (csrc/mvanet.hip)
-MVANET_MAX_RATIOS = _abi_mvanet.constants["MI355X_MVANET_MAX_RATIOS"]
+MVANET_MAX_RATIOS = ABIS["mvanet"].constants["MI355X_MVANET_MAX_RATIOS"]
 
 
 def mvanet_pool_rows(G: int, ratios: Sequence[int]) -> int:
@@ -1493,8 +1458,8 @@ def glu_silu(x: Tensor, out: Tensor) -> Tensor:
 
 
 # ------------------------------------------------------------------------------------------------ InformativeDrawings (csrc/lineart.hip)
-LINEART_ROWS, LINEART_PADDED, LINEART_QUAD = (_abi_lineart.constants[f"MI355X_LINEART_{n}"] for n in ("ROWS", "PADDED", "QUAD"))
-LINEART_MAX_CIN = _abi_lineart.constants["MI355X_LINEART_MAX_CIN"]
+LINEART_ROWS, LINEART_PADDED, LINEART_QUAD = (ABIS["lineart"].constants[f"MI355X_LINEART_{n}"] for n in ("ROWS", "PADDED", "QUAD"))
+LINEART_MAX_CIN = ABIS["lineart"].constants["MI355X_LINEART_MAX_CIN"]
 
 
 def lineart_rows(B: int, H: int, W: int, layout: int = LINEART_ROWS, pad: int = 0) -> int:

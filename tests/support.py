@@ -41,6 +41,21 @@ def golden(case: str) -> dict[str, torch.Tensor]:
     return {k: torch.cat([p[k] for p in parts if k in p]) for k in names}
 
 
+def c_compiler() -> str:
+    """The host C compiler, or the clang that hipcc drives; none at all fails the test."""
+    import shutil
+
+    import pytest
+
+    from refiners_amd.build_native import hipcc_path
+
+    rocm = Path(hipcc_path()).resolve().parent.parent
+    for cc in ("cc", "gcc", "clang", rocm / "llvm/bin/clang", rocm / "lib/llvm/bin/clang"):
+        if shutil.which(str(cc)):
+            return shutil.which(str(cc))
+    pytest.fail("no C compiler found (cc, gcc, clang, or the clang next to hipcc)")
+
+
 def manifest() -> dict[str, Any]:
     return json.loads((GOLD / "manifest.json").read_text())
 

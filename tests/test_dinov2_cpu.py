@@ -11,7 +11,7 @@ import torch
 import torch.nn.functional as F
 
 import refiners_amd.fluxion.layers as fl
-from refiners_amd import abi, native
+from refiners_amd import native
 from refiners_amd import dinov2 as DV
 from refiners_amd.engine import dinov2 as ED
 from refiners_amd.engine.packing import Unsupported
@@ -122,16 +122,6 @@ def test_layer_scale_fold_equals_the_residual():
         want = res(x)
     got = x + inner @ w.t() + b
     assert float((got - want).abs().max()) < 1e-12
-
-
-# ------------------------------------------------------------------------------------------------ ABI
-def test_exports_equal_the_header_and_are_disjoint():
-    header = abi.HEADER.parent / "mi355x_refiners_dinov2.h"
-    parsed = abi.read(native.DINOV2_STRUCT_NAMES, header)
-    assert native.EXPORTS_DINOV2 == list(parsed.functions) == ["mi355x_dinov2_pos_resample", "mi355x_dinov2_tokens", "mi355x_glu_silu"]
-    others = native.EXPORTS + native.EXPORTS_SAM_HQ + native.EXPORTS_SOLVER_STEP + native.EXPORTS_SWIN + native.EXPORTS_MVANET
-    assert not set(native.EXPORTS_DINOV2) & set(others)
-    assert set(native.DINOV2_STRUCT_NAMES) == set(parsed.structs) and "double" not in header.read_text()
 
 
 # ------------------------------------------------------------------------------------------------ dry lowerings

@@ -79,36 +79,15 @@ def test_zero_initialised_modulation_is_the_identity():
 
 
 # ------------------------------------------------------------------------------------------------ the header
-def test_ella_header_is_bound_and_exported(tmp_path):
-    """include/mi355x_refiners_ella.h: its entry point is in the built library, EXPORTS_ELLA is what the header declares, and the C compiler lays
-    the struct out as refiners_amd.abi reads it (the check tests/test_abi_header_cpu.py makes for mi355x_refiners.h)."""
+def test_ella_header_is_bound_and_exported():
+    """The ELLA header's prototype written out by hand (its names, layout and exports: tests/test_abi_header_cpu.py)."""
     import ctypes as C
-    import re
-    import shutil
-    import subprocess
 
-    from refiners_amd.build_native import DEPS, HEADERS, SOURCES, build_native, hipcc_path
+    from refiners_amd.build_native import build_native
 
-    header = ROOT / "include" / "mi355x_refiners_ella.h"
-    declared = re.findall(r"^int (mi355x_[a-z0-9_]+)\s*\(", header.read_text(), flags=re.M)
-    assert native.EXPORTS_ELLA == declared == ["mi355x_ella_adaln"] and not set(native.EXPORTS_ELLA) & set(native.EXPORTS)
-    assert "ella.hip" in SOURCES and "../../include/mi355x_refiners_ella.h" in HEADERS and "../../include/mi355x_refiners_ella.h" in DEPS["ella.hip"]
     build_native()
     lib = native.load()
     assert hasattr(lib, "mi355x_ella_adaln") and lib.mi355x_ella_adaln.argtypes == [C.POINTER(native.EllaAdaLnArgs), C.c_void_p]
-    rocm = Path(hipcc_path()).resolve().parent.parent
-    cc = next((shutil.which(str(c)) for c in ("cc", "gcc", "clang", rocm / "llvm/bin/clang", rocm / "lib/llvm/bin/clang") if shutil.which(str(c))), None)
-    assert cc, "no C compiler found"
-    cls = native.EllaAdaLnArgs
-    lines = ["#include <stddef.h>", "#include <stdio.h>", f'#include "{header}"', "int main(void) {", '    printf("%zu\\n", sizeof(mi355x_ella_adaln_args));']
-    ours = [C.sizeof(cls)]
-    for field, (name, _t) in zip(cls._c_fields_, cls._fields_):
-        lines.append(f'    printf("%zu\\n", offsetof(mi355x_ella_adaln_args, {field}));')
-        ours.append(getattr(cls, name).offset)
-    (tmp_path / "layout.c").write_text("\n".join(lines + ["    return 0;", "}"]) + "\n")
-    subprocess.run([cc, "-std=c99", "-Wall", "-Werror", "-o", str(tmp_path / "layout"), str(tmp_path / "layout.c")], check=True, capture_output=True, text=True)
-    out = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout
-    assert [int(v) for v in out.split()] == ours
 
 
 # ------------------------------------------------------------------------------------------------ dry lowerings

@@ -3,9 +3,6 @@ phase-weight packing of the transposed convolution and the ring index helper aga
 lowerings on the meta device and the fallbacks."""
 import ctypes as C
 import os
-import re
-import shutil
-import subprocess
 import sys
 import warnings
 from collections import Counter
@@ -96,37 +93,14 @@ def test_reflected_3x3_is_the_interior_of_the_zero_padded_one():
 
 
 # ------------------------------------------------------------------------------------------------ ABI
-def test_lineart_header_is_bound_and_exported(tmp_path):
-    """include/mi355x_refiners_lineart.h: its entry points are in the built library, EXPORTS_LINEART is what the header declares, and the C
-    compiler lays the structs out as refiners_amd.abi reads them (the check tests/test_abi_header_cpu.py makes for mi355x_refiners.h)."""
-    from refiners_amd.build_native import DEPS, HEADERS, SOURCES, build_native, hipcc_path
+def test_lineart_header_is_bound_and_exported():
+    """Two prototypes of the lineart header written out by hand (its names, layouts and exports: tests/test_abi_header_cpu.py), and its one
+    host-side function."""
+    from refiners_amd.build_native import build_native
 
-    header = ROOT / "include" / "mi355x_refiners_lineart.h"
-    declared = re.findall(r"^(?:int|int64_t) (mi355x_[a-z0-9_]+)\s*\(", header.read_text(), flags=re.M)
-    assert native.EXPORTS_LINEART == declared == ["mi355x_lineart_stem", "mi355x_lineart_in_stats", "mi355x_lineart_in_stats_ws_floats", "mi355x_lineart_in_apply", "mi355x_lineart_head"]
-    others = native.EXPORTS + native.EXPORTS_SAM_HQ + native.EXPORTS_SOLVER_STEP + native.EXPORTS_SWIN + native.EXPORTS_MVANET + native.EXPORTS_DINOV2 + native.EXPORTS_ELLA
-    assert not set(native.EXPORTS_LINEART) & set(others) and "double" not in header.read_text()
-    assert "lineart.hip" in SOURCES and "../../include/mi355x_refiners_lineart.h" in HEADERS and "../../include/mi355x_refiners_lineart.h" in DEPS["lineart.hip"]
     build_native()
     lib = native.load()
-    assert all(hasattr(lib, s) for s in declared)
     assert lib.mi355x_lineart_head.argtypes == [C.POINTER(native.LineartHeadArgs), C.c_void_p] and lib.mi355x_lineart_in_stats_ws_floats.restype == C.c_int64
-    rocm = Path(hipcc_path()).resolve().parent.parent
-    cc = next((shutil.which(str(c)) for c in ("cc", "gcc", "clang", rocm / "llvm/bin/clang", rocm / "lib/llvm/bin/clang") if shutil.which(str(c))), None)
-    assert cc, "no C compiler found"
-    lines = ["#include <stddef.h>", "#include <stdio.h>", f'#include "{header}"', "int main(void) {"]
-    ours = []
-    for cname, pyname in native.LINEART_STRUCT_NAMES.items():
-        cls = getattr(native, pyname)
-        lines.append(f'    printf("%zu\\n", sizeof({cname}));')
-        ours.append(C.sizeof(cls))
-        for field, (name, _t) in zip(cls._c_fields_, cls._fields_):
-            lines.append(f'    printf("%zu\\n", offsetof({cname}, {field}));')
-            ours.append(getattr(cls, name).offset)
-    (tmp_path / "layout.c").write_text("\n".join(lines + ["    return 0;", "}"]) + "\n")
-    subprocess.run([cc, "-std=c99", "-Wall", "-Werror", "-o", str(tmp_path / "layout"), str(tmp_path / "layout.c")], check=True, capture_output=True, text=True)
-    out = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout
-    assert [int(v) for v in out.split()] == ours
     # the scratch the statistics ask for is host arithmetic: slabs x columns x (mean, M2), four column groups for the quadrant layout
     assert native.lineart_in_stats_ws_floats(1, 2, 3, 64) == 1 * 64 * 2 and native.lineart_in_stats_ws_floats(2, 4, 6, 64, native.LINEART_QUAD) == 2 * 256 * 2
     assert native.lineart_in_stats_ws_floats(1, 512, 512, 64) == 1024 * 64 * 2 and native.lineart_in_stats_ws_floats(1, 19, 25, 128) == 4 * 128 * 2

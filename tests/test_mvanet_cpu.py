@@ -210,17 +210,6 @@ def test_compiled_falls_back_to_the_stock_forward_with_a_warning():
         net(torch.zeros(2, 3, 64, 64))  # the stock forward is what runs (and raises, as the reference does for this shape)
 
 
-def test_exports_are_the_headers_and_disjoint():
-    header = (Path(__file__).resolve().parent.parent / "include" / "mi355x_refiners_mvanet.h").read_text()
-    import re
-
-    declared = re.findall(r"^int (mi355x_\w+)\(", header, flags=re.M)
-    assert native.EXPORTS_MVANET == declared and len(declared) == 5
-    others = native.EXPORTS + native.EXPORTS_SAM_HQ + native.EXPORTS_SOLVER_STEP + native.EXPORTS_SWIN
-    assert not set(declared) & set(others)
-    assert set(native.MVANET_STRUCT_NAMES.values()) <= set(dir(native))
-
-
 @pytest.mark.skipif(not (REF / "refiners").exists(), reason="no refiners package (REFINERS_SRC / oracle/_ref, staged by build())")
 def test_lowering_accepts_the_real_refiners_tree():
     root = Path(__file__).resolve().parent.parent

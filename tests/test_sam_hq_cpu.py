@@ -76,37 +76,16 @@ def test_two_adapters_keep_their_own_weights():
 
 
 # ------------------------------------------------------------------------------------------------ the ABI extension
-def test_sam_hq_header_is_bound_and_exported(tmp_path):
-    """include/mi355x_refiners_sam_hq.h: the three entry points are in the built library, and the C compiler lays its two structs out as
-    refiners_amd.abi reads them (the check tests/test_abi_header_cpu.py makes for mi355x_refiners.h)."""
+def test_sam_hq_header_is_bound_and_exported():
+    """Two prototypes of the HQ-SAM header written out by hand (its names, layouts and exports: tests/test_abi_header_cpu.py)."""
     import ctypes as C
-    import shutil
-    import subprocess
 
     from refiners_amd import native
-    from refiners_amd.build_native import build_native, hipcc_path
+    from refiners_amd.build_native import build_native
 
-    assert native.EXPORTS_SAM_HQ == ["mi355x_sam_hq_mask_head", "mi355x_sam_mask_head_up", "mi355x_ln2d_gelu_wide"] and not set(native.EXPORTS_SAM_HQ) & set(native.EXPORTS)
     build_native()
     lib = native.load()
-    assert all(hasattr(lib, name) for name in native.EXPORTS_SAM_HQ)
     assert lib.mi355x_sam_hq_mask_head.argtypes == [C.POINTER(native.SamHqMaskHeadArgs), C.c_void_p] and len(lib.mi355x_ln2d_gelu_wide.argtypes) == 13
-    rocm = Path(hipcc_path()).resolve().parent.parent
-    cc = next((shutil.which(str(c)) for c in ("cc", "gcc", "clang", rocm / "llvm/bin/clang", rocm / "lib/llvm/bin/clang") if shutil.which(str(c))), None)
-    assert cc, "no C compiler found"
-    structs = {"mi355x_sam_hq_mask_head_args": native.SamHqMaskHeadArgs, "mi355x_sam_mask_head_up_args": native.SamMaskHeadUpArgs}
-    lines = ["#include <stddef.h>", "#include <stdio.h>", f'#include "{ROOT / "include" / "mi355x_refiners_sam_hq.h"}"', "int main(void) {"]
-    ours = []
-    for cname_, cls in structs.items():
-        lines.append(f'    printf("%zu\\n", sizeof({cname_}));')
-        ours.append(C.sizeof(cls))
-        for field, (name, _t) in zip(cls._c_fields_, cls._fields_):
-            lines.append(f'    printf("%zu\\n", offsetof({cname_}, {field}));')
-            ours.append(getattr(cls, name).offset)
-    (tmp_path / "layout.c").write_text("\n".join(lines + ["    return 0;", "}"]) + "\n")
-    subprocess.run([cc, "-std=c99", "-Wall", "-Werror", "-o", str(tmp_path / "layout"), str(tmp_path / "layout.c")], check=True, capture_output=True, text=True)
-    out = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout
-    assert [int(v) for v in out.split()] == ours
 
 
 # ------------------------------------------------------------------------------------------------ the fold
