@@ -1,5 +1,5 @@
 /*
- * mi355x_refiners_sde_step.h -- the stochastic solver updates of libmi355x_refiners.so (refiners_amd/csrc/sde_step.hip).
+ * mi355x_refiners_sde_step.h -- the stochastic solver updates of libmi355x_refiners.so (refiners_amd/csrc/solver_step.hip).
  *
  * An extension of mi355x_refiners.h with the conventions of mi355x_refiners_solver_step.h: plain C, raw device pointers, `stream` a
  * hipStream_t passed as void*, dtype = MI355X_F32 (0) or MI355X_BF16 (1), return value 0 or one of mi355x_refiners.h's negative

@@ -14,7 +14,7 @@ from pathlib import Path
 
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = CSRC / "libmi355x_refiners.so"
-SOURCES = ["gemm.hip", "gemm_conv.hip", "gemm_xattn.hip", "gemm8.hip", "attention.hip", "attention_general.hip", "norm.hip", "elementwise.hip", "sam_decoder.hip", "sam_hq.hip", "window_attention.hip", "mvanet.hip", "dinov2.hip", "ella.hip", "lineart.hip", "reference_only.hip", "style_aligned.hip", "multi_diffusion.hip", "tiled_vae.hip", "solver_step.hip", "cond_input.hip", "sde_step.hip"]
+SOURCES = ["gemm.hip", "gemm_conv.hip", "gemm_xattn.hip", "gemm8.hip", "attention.hip", "attention_general.hip", "norm.hip", "elementwise.hip", "sam_decoder.hip", "sam_hq.hip", "window_attention.hip", "mvanet.hip", "dinov2.hip", "ella.hip", "lineart.hip", "reference_only.hip", "style_aligned.hip", "multi_diffusion.hip", "tiled_vae.hip", "solver_step.hip", "cond_input.hip"]
 ARCH = "gfx950"
 CORE_HEADER = "../../include/mi355x_refiners.h"  # every object depends on it unconditionally, so DEPS leaves it out
 

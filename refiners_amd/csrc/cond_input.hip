@@ -1,6 +1,6 @@
 // Step-constant UNet input channels (SD1.5 inpainting, IC-Light): the UNet reads model_in [n or 2n][C + E][hw] while the latents stay [n][C][hw].
-//   cond_step            the step's last launch: the latent update of the four existing step kernels (solver_update.cuh's device functions, so x and
-//                        hist are bit-equal to them) + the next step's model input, latents re-strided into C + E channel images, constants rescaled
+//   cond_step            the step's last launch: the latent update of the batch step kernel (solver_step.hip; solver_update.cuh's step_elem, so x and
+//                        hist are bit-equal to it) + the next step's model input, latents re-strided into C + E channel images, constants rescaled
 //   cond_fill            primes a model input from x and / or the constants (first step; the second pass of Self-Attention Guidance)
 //   inpaint_conditions   uint8 image + mask -> masked image in [-1, 1] and the nearest-resampled binary mask (set_inpainting_conditions minus the VAE)
 // HBM-bound streaming kernels of a few hundred KB: 16-byte vectors when a channel row is a whole number of them and every pointer is aligned,
@@ -32,22 +32,16 @@ inline bool overlaps(const void* a, int64_t ab, const void* b, int64_t bb) {
     return a0 < b0 + (uintptr_t)bb && b0 < a0 + (uintptr_t)ab;
 }
 
-// One latent element.  eps = fma(cfg, c - u, u) is what mi355x_cfg_ddim_step / mi355x_cfg_linear_step compute (the list in solver_update.cuh).
-template <typename T, bool LINEAR, bool GUIDED> MI_DEV float step_elem(float xv, float u, float c, float hv, const float (&k)[8], float& d) {
-    const float eps = GUIDED ? fmaf(k[0], c - u, u) : u;
-    if constexpr (LINEAR) return linear_update<T>(xv, eps, hv, k[1], k[2], k[3], k[4], k[5], k[6], d);
-    d = 0.0f;
-    return ddim_update(xv, eps, k[1], k[2], k[3], k[4]);
-}
-
 // chw = C * hw, ehw = E * hw (elements per image); VEC: both are multiples of EPC and every pointer is 16-byte aligned.
 // Units [0, n * chw / U) are the latents, the B * ehw / U behind them the constants (cond != NULL), U = EPC or 1, B = 2n guided, n not.
+// One latent element is step_elem (solver_update.cuh), as in the batch kernel (solver_step.hip); the addressing is this kernel's own.
 template <typename T, bool LINEAR, bool GUIDED, bool VEC>
 __global__ __launch_bounds__(256) void cond_step_kernel(T* __restrict__ x, const T* __restrict__ uo, T* __restrict__ hist, T* __restrict__ model_in,
                                                          const T* __restrict__ cond, const float* __restrict__ coef, int n, int nc, int64_t chw,
                                                          int64_t ehw) {
     constexpr int U = VEC ? DT<T>::EPC : 1;
-    float k[8];
+    constexpr StepForm FORM = LINEAR ? STEP_LINEAR : STEP_DDIM;
+    float k[9] = {};
 #pragma unroll
     for (int i = 0; i < 8; ++i) k[i] = coef[i];
     const float sn = LINEAR ? k[7] : 1.0f;
@@ -65,7 +59,7 @@ __global__ __launch_bounds__(256) void cond_step_kernel(T* __restrict__ x, const
 #pragma unroll
                 for (int e = 0; e < U; ++e) {
                     float d;
-                    xo.set(e, step_elem<T, LINEAR, GUIDED>(xv.get(e), uv.get(e), cv.get(e), hv.get(e), k, d));
+                    xo.set(e, step_elem<T, FORM, GUIDED>(xv.get(e), uv.get(e), cv.get(e), hv.get(e), 0.0f, k, d));
                     ho.set(e, d);
                     mo.set(e, sn * xo.get(e));  // the next step scales the STORED latents, as solver.scale_model_input does
                 }
@@ -76,7 +70,7 @@ __global__ __launch_bounds__(256) void cond_step_kernel(T* __restrict__ x, const
             } else {
                 float d;
                 const float u = to_f32(uo[i]), c = GUIDED ? to_f32(uo[(int64_t)n * chw + i]) : u, hv = LINEAR ? to_f32(hist[i]) : 0.0f;
-                const T xs = from_f32<T>(step_elem<T, LINEAR, GUIDED>(to_f32(x[i]), u, c, hv, k, d));
+                const T xs = from_f32<T>(step_elem<T, FORM, GUIDED>(to_f32(x[i]), u, c, hv, 0.0f, k, d));
                 x[i] = xs;
                 if constexpr (LINEAR) hist[i] = from_f32<T>(d);
                 const T mi = LINEAR ? from_f32<T>(sn * to_f32(xs)) : xs;

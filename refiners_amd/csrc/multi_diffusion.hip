@@ -8,6 +8,7 @@
 // The sums of gather's add_noise form and of blend are single-rounding operations (no fused multiply-add: contraction is off in this file), which is
 // what torch's separate mul / add kernels compute: in float32 both passes give the reference's bits.
 #include "common.cuh"
+#include "solver_update.cuh"
 #include "../../include/mi355x_refiners.h"
 
 // every product and sum below is rounded on its own unless it is written as fmaf(): the float32 results are compared bit for bit with torch's
@@ -96,36 +97,17 @@ __global__ __launch_bounds__(256) void md_gather_kernel(const T* __restrict__ ca
     }
 }
 
-// The two update forms, element by element.  mi355x_cfg_ddim_step / mi355x_cfg_linear_step (elementwise.hip) leave the fusing of products into sums to the
-// compiler; this file is compiled with contraction off (the pragma below the includes) and spells out what the compiler chose there, so that a target
-// under its own coefficient row gets the bits the batch kernels give it (tests/test_multi_diffusion_kernels_gpu.py compares them at T = 1):
-//   eps = fma(cfg, c - u, u)                                                        both forms, both storage types
-//   DDIM    x0 = fma(-sqrt(1 - a_t), eps, x) / sqrt(a_t);  x' = sqrt(a_prev) x0 + sqrt(1 - a_prev) eps    (two products, one sum)
-//   linear  d = fma(hx, x, he eps) in float32 storage, hx x + he eps (unfused) in bf16;  x' = fma(kp, hist, fma(kd, d, fma(kx, x, ke eps)))
-template <typename T> MI_DEV T ddim_elem(float xv, float u, float c, float cfg, float sa, float s1a, float sap, float s1ap) {
-    const float eps = fmaf(cfg, c - u, u);
-    const float x0 = fmaf(-s1a, eps, xv) / sa;
-    return from_f32<T>(sap * x0 + s1ap * eps);
-}
-template <typename T> MI_DEV T linear_elem(float xv, float u, float c, float hv, float cfg, float hx, float he, float kx, float ke, float kd, float kp, T& hout) {
-    const float eps = fmaf(cfg, c - u, u);
-    float d;
-    if constexpr (sizeof(T) == 4)
-        d = fmaf(hx, xv, he * eps);
-    else
-        d = hx * xv + he * eps;
-    const float xn = fmaf(kp, hv, fmaf(kd, d, fmaf(kx, xv, ke * eps)));
-    hout = from_f32<T>(d);
-    return from_f32<T>(xn);
-}
-
 // grid (blocks, T).  coef + 8 t: {cfg, sqrt(a_t), sqrt(1 - a_t), sqrt(a_prev), sqrt(1 - a_prev)} (LINEAR == false) or {cfg, hx, he, kx, ke, kd, kp, -}.
+// One element is the guided step_elem of the batch kernel (solver_update.cuh, solver_step.hip), so a target under its own coefficient row gets the bits
+// the batch gets (tests/test_multi_diffusion_kernels_gpu.py compares them at T = 1).
 template <typename T, int VEC, bool LINEAR>
 __global__ __launch_bounds__(256) void md_target_step_kernel(const T* __restrict__ view, const T* __restrict__ uo, T* __restrict__ stepped, T* __restrict__ hist,
                                                               const float* __restrict__ coef, int nt, int64_t n) {
+    constexpr StepForm FORM = LINEAR ? STEP_LINEAR : STEP_DDIM;
     const int t = blockIdx.y;
-    const float* k = coef + 8 * t;
-    const float k0 = k[0], k1 = k[1], k2 = k[2], k3 = k[3], k4 = k[4], k5 = k[5], k6 = k[6];
+    float k[9] = {};
+#pragma unroll
+    for (int i = 0; i < 7; ++i) k[i] = coef[8 * t + i];
     const T* xv = view + (int64_t)t * n;
     const T* u = uo + (int64_t)t * n;
     const T* c = uo + (int64_t)(nt + t) * n;
@@ -140,10 +122,10 @@ __global__ __launch_bounds__(256) void md_target_step_kernel(const T* __restrict
         if constexpr (LINEAR) load_n<T, VEC>(ho + i, hh);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
-            if constexpr (LINEAR)
-                o[e] = linear_elem<T>(to_f32(a[e]), to_f32(b[e]), to_f32(g[e]), to_f32(hh[e]), k0, k1, k2, k3, k4, k5, k6, hh[e]);
-            else
-                o[e] = ddim_elem<T>(to_f32(a[e]), to_f32(b[e]), to_f32(g[e]), k0, k1, k2, k3, k4);
+            float hv = 0.0f, d;
+            if constexpr (LINEAR) hv = to_f32(hh[e]);
+            o[e] = from_f32<T>(step_elem<T, FORM, true>(to_f32(a[e]), to_f32(b[e]), to_f32(g[e]), hv, 0.0f, k, d));
+            if constexpr (LINEAR) hh[e] = from_f32<T>(d);
         }
         store_n<T, VEC>(so + i, o);
         if constexpr (LINEAR) store_n<T, VEC>(ho + i, hh);

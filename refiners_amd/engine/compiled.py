@@ -664,21 +664,31 @@ class CompiledSDXL:
         gkey = ("pair", eu.key, ec.key)
         if self.linear:
             return self._linear_step(step, io, None, eu, None, gkey, run=self._replay_pair)
-        if not self.use_graph:
+        return self._guided_ddim_step(io, self._replay_pair, None, gkey)
+
+    def _guided_ddim_step(self, io: Any, run: Any, tail: Any, gkey: Any) -> Tensor:
+        """Guided DDIM without step-constant channels: copy x into both halves of the model input, run the UNet program (`run`), the
+        Self-Attention-Guidance pass if there is one (`tail`), and mi355x_cfg_ddim_step -- launched directly, or captured once per `gkey`."""
+        assert self.x is not None
+
+        def body(last: bool = True) -> None:
             self._fill(io)
-            self._replay_pair()
-            native.cfg_ddim_step(self.x, io.out, self.coef)
+            run()
+            if tail is not None:
+                tail()
+            if last:
+                native.cfg_ddim_step(self.x, io.out, self.coef)
+
+        if not self.use_graph:
+            body()
             return self.x
         if self.graph is None or self.graph_key != gkey:
             keep = self.x.clone()
-            self._fill(io)
-            self._replay_pair()  # warm-up outside capture
+            body(last=False)  # warm-up outside capture (first-launch attribute calls, workspaces)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._fill(io)
-                self._replay_pair()
-                native.cfg_ddim_step(self.x, io.out, self.coef)
+                body()
             self.x.copy_(keep)
             self.graph, self.graph_key = g, gkey
         self.graph.replay()
@@ -739,14 +749,18 @@ class CompiledSDXL:
         """The step's last launch: (guidance +) solver update + history + the next step's model input."""
         if self.cond is not None:
             native.cond_step(self.x, io.out, self.hist, io.x, self.cond if self.scales_input else None, self.coef, self.linear, self._cfg)
-        elif self.sde:
-            (native.cfg_sde_step if self._cfg else native.sde_step)(self.x, io.out, self.hist, self.sde_noise, io.x, self.coef)
-        elif self._cfg:
-            native.cfg_linear_step(self.x, io.out, self.hist, io.x, self.coef)
-        elif self.linear:
-            native.linear_step(self.x, io.out, self.hist, io.x, self.coef)
-        else:
-            native.ddim_step(self.x, io.out, io.x, self.coef)
+            return
+        name, operands = self._UPDATES[(self.sde, self.linear, self._cfg)]  # (guided DDIM is not here: _guided_ddim_step)
+        getattr(native, name)(self.x, io.out, *(getattr(self, a) for a in operands), io.x, self.coef)
+
+    #: (stochastic, linear, guided) -> the wrapper in `native` and the operands it takes between the UNet's output and the model input
+    _UPDATES = {
+        (True, True, True): ("cfg_sde_step", ("hist", "sde_noise")),
+        (True, True, False): ("sde_step", ("hist", "sde_noise")),
+        (False, True, True): ("cfg_linear_step", ("hist",)),
+        (False, True, False): ("linear_step", ("hist",)),
+        (False, False, False): ("ddim_step", ()),
+    }
 
     @torch.no_grad()
     def step(self, step: int) -> Tensor:
@@ -789,30 +803,7 @@ class CompiledSDXL:
         gkey = (eng.key, None if self.engine2 is None or sag is None else (self.engine2.key, float(sag.scale) / float(self.condition_scale), int(sag.kernel_size), float(sag.sigma))) + self._cond_id()
         if self.linear or self.cond is not None:  # (with step-constant channels DDIM too keeps its model input primed: mi355x_cond_step writes the next one)
             return self._linear_step(step, io, low, eng, tail, gkey)
-        if tail is None:
-            tail = lambda: None  # noqa: E731
-        if not self.use_graph:
-            self._fill()
-            native.replay(low.step)
-            tail()
-            native.cfg_ddim_step(self.x, io.out, self.coef)
-            return self.x
-        if self.graph is None or self.graph_key != gkey:
-            keep = self.x.clone()
-            self._fill()
-            native.replay(low.step)  # warm-up outside capture (first-launch attribute calls, workspaces)
-            tail()
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._fill()
-                native.replay(low.step)
-                tail()
-                native.cfg_ddim_step(self.x, io.out, self.coef)
-            self.x.copy_(keep)
-            self.graph, self.graph_key = g, gkey
-        self.graph.replay()
-        return self.x
+        return self._guided_ddim_step(io, lambda: native.replay(low.step), tail, gkey)
 
     def _cond_id(self) -> tuple:
         """What a captured graph holds of the step-constant channels: the buffer's address and shape, and whether the last launch rescales them."""

@@ -1037,70 +1037,57 @@ def silu(x: Tensor, out: Tensor) -> Tensor:
     return out
 
 
+_NO = object()  # an operand the entry point's prototype does not have (None is an operand passed as NULL)
+
+
+def _solver_step(sym: str, rows: int, ncoef: int, x: Tensor, unet_out: Tensor, hist: Any, noise: Any, model_in: Any, coef: Tensor) -> Tensor:
+    """The launch behind the six solver-step wrappers below (csrc/solver_step.hip): x, hist, noise have n elements, unet_out and model_in
+    rows * n (rows = 2: the CFG pair); model_in may be None; coef: at least `ncoef` float32 on the device."""
+    ops = [t for t in (hist, noise) if t is not _NO]
+    assert x.is_contiguous() and unet_out.is_contiguous() and all(t.is_contiguous() for t in ops) and rows in (1, 2)
+    assert unet_out.numel() == rows * x.numel() and all(t.numel() == x.numel() for t in ops)
+    assert unet_out.dtype == x.dtype and all(t.dtype == x.dtype for t in ops)
+    assert coef.dtype == torch.float32 and coef.numel() >= ncoef and coef.is_cuda
+    assert model_in is _NO or model_in is None or (
+        model_in.is_contiguous() and model_in.numel() == rows * x.numel() and model_in.dtype == x.dtype and model_in.data_ptr() != x.data_ptr())
+    ptrs = [None if t is None else t.data_ptr() for t in (hist, noise, model_in) if t is not _NO]
+    _launch(sym, (dtype_code(x.dtype), x.data_ptr(), unet_out.data_ptr(), *ptrs, coef.data_ptr(), x.numel()), sym, keep=() if noise is _NO else (noise,))
+    return x
+
+
 def cfg_ddim_step(x: Tensor, unet_out: Tensor, coef: Tensor) -> Tensor:
     """In-place: x <- ddim(x, cfg(unet_out)). unet_out = [uncond; cond] (2*x.numel() elements); coef: f32[5] on device."""
-    assert x.is_contiguous() and unet_out.is_contiguous() and unet_out.numel() == 2 * x.numel()
-    assert coef.dtype == torch.float32 and coef.numel() >= 5 and coef.is_cuda
-    _launch("mi355x_cfg_ddim_step", (dtype_code(x.dtype), x.data_ptr(), unet_out.data_ptr(), coef.data_ptr(), x.numel(),), "mi355x_cfg_ddim_step")
-    return x
+    return _solver_step("mi355x_cfg_ddim_step", 2, 5, x, unet_out, _NO, _NO, _NO, coef)
 
 
 def cfg_linear_step(x: Tensor, unet_out: Tensor, hist: Tensor, model_in: Optional[Tensor], coef: Tensor) -> Tensor:
     """x, hist: [N, ...] latents (in place); unet_out: [2N, ...] = (unconditional, conditional); model_in: [2N, ...] or None;
     coef: 8 float32 on the device = (cfg, hx, he, kx, ke, kd, kp, s_next) -- see mi355x_cfg_linear_step in the header."""
-    assert x.is_contiguous() and unet_out.is_contiguous() and hist.is_contiguous() and unet_out.numel() == 2 * x.numel() == 2 * hist.numel()
-    assert coef.dtype == torch.float32 and coef.numel() >= 8 and (model_in is None or (model_in.is_contiguous() and model_in.numel() == 2 * x.numel()))
-    _launch("mi355x_cfg_linear_step", (dtype_code(x.dtype), x.data_ptr(), unet_out.data_ptr(), hist.data_ptr(), model_in.data_ptr() if model_in is not None else None,
-                                      coef.data_ptr(), x.numel()), "mi355x_cfg_linear_step")
-    return x
+    return _solver_step("mi355x_cfg_linear_step", 2, 8, x, unet_out, hist, _NO, model_in, coef)
 
 
 def ddim_step(x: Tensor, unet_out: Tensor, model_in: Optional[Tensor], coef: Tensor) -> Tensor:
     """Guidance-free DDIM update, in place: x <- ddim(x, unet_out); model_in (x's shape, or None) <- the new x, the next step's model input.
     coef: the 8-float row of cfg_ddim_step on the device (coef[0], the guidance scale, is not read) -- see mi355x_ddim_step in its header."""
-    assert x.is_contiguous() and unet_out.is_contiguous() and unet_out.numel() == x.numel() and unet_out.dtype == x.dtype
-    assert coef.dtype == torch.float32 and coef.numel() >= 5 and coef.is_cuda
-    assert model_in is None or (model_in.is_contiguous() and model_in.numel() == x.numel() and model_in.dtype == x.dtype and model_in.data_ptr() != x.data_ptr())
-    _launch("mi355x_ddim_step", (dtype_code(x.dtype), x.data_ptr(), unet_out.data_ptr(), model_in.data_ptr() if model_in is not None else None,
-                                coef.data_ptr(), x.numel()), "mi355x_ddim_step")
-    return x
+    return _solver_step("mi355x_ddim_step", 1, 5, x, unet_out, _NO, _NO, model_in, coef)
 
 
 def linear_step(x: Tensor, unet_out: Tensor, hist: Tensor, model_in: Optional[Tensor], coef: Tensor) -> Tensor:
     """Guidance-free form of cfg_linear_step: x, hist, unet_out and model_in (or None) all have x's n elements; coef: 8 float32 on the device =
     (-, hx, he, kx, ke, kd, kp, s_next) -- see mi355x_linear_step in its header."""
-    assert x.is_contiguous() and unet_out.is_contiguous() and hist.is_contiguous() and unet_out.numel() == x.numel() == hist.numel()
-    assert unet_out.dtype == x.dtype == hist.dtype
-    assert coef.dtype == torch.float32 and coef.numel() >= 8 and (model_in is None or (model_in.is_contiguous() and model_in.numel() == x.numel() and model_in.dtype == x.dtype))
-    _launch("mi355x_linear_step", (dtype_code(x.dtype), x.data_ptr(), unet_out.data_ptr(), hist.data_ptr(), model_in.data_ptr() if model_in is not None else None,
-                                  coef.data_ptr(), x.numel()), "mi355x_linear_step")
-    return x
-
-
-def _sde_step_checks(x: Tensor, unet_out: Tensor, hist: Tensor, noise: Tensor, model_in: Optional[Tensor], coef: Tensor, rows: int) -> None:
-    assert x.is_contiguous() and unet_out.is_contiguous() and hist.is_contiguous() and noise.is_contiguous()
-    assert unet_out.numel() == rows * x.numel() and hist.numel() == x.numel() == noise.numel()
-    assert unet_out.dtype == x.dtype == hist.dtype == noise.dtype
-    assert coef.dtype == torch.float32 and coef.numel() >= 9 and coef.is_cuda
-    assert model_in is None or (model_in.is_contiguous() and model_in.numel() == rows * x.numel() and model_in.dtype == x.dtype and model_in.data_ptr() != x.data_ptr())
+    return _solver_step("mi355x_linear_step", 1, 8, x, unet_out, hist, _NO, model_in, coef)
 
 
 def cfg_sde_step(x: Tensor, unet_out: Tensor, hist: Tensor, noise: Tensor, model_in: Optional[Tensor], coef: Tensor) -> Tensor:
     """cfg_linear_step with the step's Gaussian draw as a fifth operand (SDE DPM-Solver++): x, hist [N, ...] in place; noise [N, ...] read only;
     unet_out [2N, ...]; model_in [2N, ...] or None; coef: 9 float32 on the device = (cfg, hx, he, kx, ke, kd, kp, s_next, kn) -- see
     mi355x_cfg_sde_step in its header."""
-    _sde_step_checks(x, unet_out, hist, noise, model_in, coef, 2)
-    _launch("mi355x_cfg_sde_step", (dtype_code(x.dtype), x.data_ptr(), unet_out.data_ptr(), hist.data_ptr(), noise.data_ptr(),
-                                   model_in.data_ptr() if model_in is not None else None, coef.data_ptr(), x.numel()), "mi355x_cfg_sde_step", keep=(noise,))
-    return x
+    return _solver_step("mi355x_cfg_sde_step", 2, 9, x, unet_out, hist, noise, model_in, coef)
 
 
 def sde_step(x: Tensor, unet_out: Tensor, hist: Tensor, noise: Tensor, model_in: Optional[Tensor], coef: Tensor) -> Tensor:
     """Guidance-free form of cfg_sde_step: unet_out and model_in (or None) have x's n elements; coef[0] is not read -- see mi355x_sde_step."""
-    _sde_step_checks(x, unet_out, hist, noise, model_in, coef, 1)
-    _launch("mi355x_sde_step", (dtype_code(x.dtype), x.data_ptr(), unet_out.data_ptr(), hist.data_ptr(), noise.data_ptr(),
-                               model_in.data_ptr() if model_in is not None else None, coef.data_ptr(), x.numel()), "mi355x_sde_step", keep=(noise,))
-    return x
+    return _solver_step("mi355x_sde_step", 1, 9, x, unet_out, hist, noise, model_in, coef)
 
 
 def _cond_geometry(x_like: tuple, model_in: Tensor, cond: Optional[Tensor]) -> tuple[int, int, int, int, int]:

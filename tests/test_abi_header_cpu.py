@@ -37,7 +37,7 @@ PINNED = {
 #: key -> the sources that include the header (every source includes the core header, which has no entry in build_native.DEPS)
 INCLUDED_BY = {"core": [], "sam_hq": ["sam_hq.hip"], "solver_step": ["solver_step.hip"], "swin": ["window_attention.hip"], "mvanet": ["mvanet.hip"], "dinov2": ["dinov2.hip"],
                "ella": ["ella.hip"], "lineart": ["lineart.hip"], "reference_only": ["reference_only.hip"], "cond_input": ["cond_input.hip"], "xattn": ["gemm_xattn.hip"],
-               "sde_step": ["sde_step.hip"]}
+               "sde_step": ["solver_step.hip"]}
 every_header =pytest.mark.parametrize("key, fname", [(key, fname) for key, fname, _names in native.ABI_HEADERS], ids=[h[0] for h in native.ABI_HEADERS])
 
 

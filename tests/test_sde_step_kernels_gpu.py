@@ -1,4 +1,4 @@
-"""pytest -m gpu: the stochastic solver updates (csrc/sde_step.hip: mi355x_cfg_sde_step, mi355x_sde_step).
+"""pytest -m gpu: the stochastic solver updates (csrc/solver_step.hip: mi355x_cfg_sde_step, mi355x_sde_step).
 
 * The guidance-free form is bit-equal to the guided one on cat(out, out) at any guidance scale: u + s (c - u) with c == u is u, and the rest
   is ONE device function (csrc/solver_update.cuh: sde_update) called from both instantiations.

@@ -1,7 +1,10 @@
-"""pytest -m gpu: the guidance-free solver updates (csrc/solver_step.hip: mi355x_ddim_step, mi355x_linear_step).
+"""pytest -m gpu: the guidance-free solver updates (csrc/solver_step.hip: mi355x_ddim_step, mi355x_linear_step), and the recorded bits of all six
+entry points of that file's one kernel.
 
-* Bit-equal to the guided kernels on cat(out, out) at any guidance scale: u + s (c - u) with c == u is u, and the rest is ONE device function
-  (csrc/solver_update.cuh) called from both files.  A difference of one bit means the two instantiations do not share the arithmetic.
+* Bit-equal to the guided entry points on cat(out, out) at any guidance scale: u + s (c - u) with c == u is u, and the rest is ONE device function
+  (csrc/solver_update.cuh) called from both instantiations.  A difference of one bit means the two instantiations do not share the arithmetic.
+* Bit-equal to what the guided one-element-per-lane kernels and the earlier vector kernels wrote (tests/golden/solver_step_bits.safetensors): the
+  test above compares the kernel with itself, this one pins it.
 * Against a float64 torch model of the formulas, with the coefficients as the kernel reads them (float32): float32 within 1e-6 (relative l2 and
   relative maximum: a handful of float32 roundings, 6e-8 each, on terms the size of the result); bfloat16 within ONE bfloat16 rounding of the float64
   result, |got - ref| <= 2^-8 |ref|, plus the float32 bound for a float32 value that sits on a rounding tie.
@@ -127,6 +130,32 @@ def test_views_off_a_16_byte_boundary_take_the_single_element_loop(dtype):
     native.ddim_step(x_a, out_a, None, _ddim_row(1.0))
     native.ddim_step(x_u, out_u, None, _ddim_row(1.0))
     assert torch.equal(x_u, x_a)
+
+
+def test_bits_are_the_parent_commits():
+    """Every entry point, on the inputs stored in tests/golden/solver_step_bits.safetensors (tests/solver_step_cases.py), writes the bits that the
+    library before the move onto one kernel wrote: the guided scalar kernels, whose fused operations the compiler chose, were the anchor of every
+    bit-equality test above and in the neighbouring files, and this record is what is left of them.  No tolerance, nothing skipped."""
+    from safetensors.torch import load_file
+
+    from tests import solver_step_cases as SC
+
+    gold = load_file(str(SC.GOLD))
+    coefs = {k: gold[k] for k in ("coef.linear", "coef.ddim")}
+    assert all(torch.equal(v, coefs[k]) for k, v in SC.coefficient_rows().items())  # the rows the issue names are the rows recorded
+    visited = 0
+    for tname, dtype in SC.DTYPES.items():
+        for layout in SC.LAYOUTS:
+            inp = {k: gold[f"{tname}.{layout}.in.{k}"] for k in ("x", "unet_out", "hist", "noise")}
+            assert all(v.dtype == dtype for v in inp.values())
+            for entry, (_, _, has_hist, _, has_model_in) in SC.ENTRIES.items():
+                got = SC.run(native, entry, layout, inp, coefs)
+                assert set(got) == {"x"} | ({"hist"} if has_hist else set()) | ({"model_in"} if has_model_in else set())
+                for k, v in got.items():
+                    want = gold[f"{tname}.{layout}.{entry}.{k}"]
+                    assert torch.equal(v, want), f"{tname} {layout} {entry}: {k} differs in {int((v != want).sum())} of {v.numel()} elements"
+                visited += 1
+    assert visited == 48
 
 
 def test_refusals_launch_nothing():
