@@ -29,6 +29,15 @@ typedef __attribute__((ext_vector_type(4))) int frag_t;   // one 16-byte operand
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
+// ---- host-side argument checks shared by the entry points ----
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }  // (NULL counts as aligned)
+// [p, p + n) and [q, q + m) (bytes) share a byte; an absent (NULL) operand overlaps nothing
+inline bool overlap(const void* p, int64_t n, const void* q, int64_t m) {
+    if (!p || !q) return false;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + (uintptr_t)m && b < a + (uintptr_t)n;
+}
+
 template <typename T> struct DT;
 template <> struct DT<float> {
     static constexpr int EPC = 4;  // elements per 16-byte chunk

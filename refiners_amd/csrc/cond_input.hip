@@ -18,7 +18,6 @@ inline int grid_for(int64_t work, int per_block = 256, int cap = 4096) {
     if (b > cap) b = cap;
     return (int)b;
 }
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // elements of an [a][b][c] tensor, or -1 when the product leaves 2^40 (no real latent does; keeps every byte count below inside int64)
 inline int64_t elems(int64_t a, int64_t b, int64_t c) {
     int64_t r;

@@ -22,16 +22,10 @@ namespace {
         }                                    \
     } while (0)
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 inline int grid_for(int64_t work, int cap = 16384) {
     int64_t b = (work + 255) / 256;
     return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-// [p, p + n) and [q, q + m) (bytes) share a byte
-inline bool overlap(const void* p, int64_t n, const void* q, int64_t m) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return a < b + (uintptr_t)m && b < a + (uintptr_t)n;
 }
 // bytes spanned by `rows` rows of E elements at stride ld
 inline int64_t span(int64_t rows, int64_t ld, int E, int es) { return ((rows - 1) * ld + E) * es; }

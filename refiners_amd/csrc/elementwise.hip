@@ -13,7 +13,6 @@ inline int grid_for(int64_t work, int per_block = 256, int cap = 4096) {
     if (b > cap) b = cap;
     return (int)b;
 }
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // NCHW -> NHWC through an LDS transpose tile: 64 pixels x 64 channels per workgroup
 template <typename T>

@@ -10,12 +10,6 @@
 
 namespace {
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-// [p, p + n) and [q, q + m) (bytes) share a byte
-inline bool overlap(const void* p, int64_t n, const void* q, int64_t m) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return a < b + (uintptr_t)m && b < a + (uintptr_t)n;
-}
 // bytes spanned by B batch rows of `rows` rows of C elements
 inline int64_t span(int64_t B, int64_t bs, int64_t rows, int64_t ld, int C, int es) { return ((B - 1) * bs + (rows - 1) * ld + C) * es; }
 

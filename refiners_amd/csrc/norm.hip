@@ -377,8 +377,6 @@ inline int gn_ppc(int B, int HW, int C, int es) {
     return ppc;
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 template <typename T>
 int run_layernorm(const mi355x_layernorm_args* a, hipStream_t st) {
     constexpr int EPC = DT<T>::EPC;

@@ -22,7 +22,6 @@ inline int grid_for(int64_t work, int per_block = 256, int cap = 4096) {
     if (b > cap) b = cap;
     return (int)b;
 }
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }  // (NULL counts as aligned)
 
 // nv = number of 16-byte vectors the vector loop covers (0 when an operand is misaligned); elements [nv * EPC, n) go through the element loop.
 // hist is read and written by LINEAR and SDE only, noise read by SDE only; model_in may be NULL (nothing written).

@@ -12,7 +12,6 @@ constexpr int SA_CT = 16;     // 16-byte channel chunks per workgroup column til
 constexpr int SA_RL = 16;     // rows a workgroup touches at once (256 threads = 16 chunks x 16 row lanes)
 constexpr int SA_ROWS = 128;  // rows per workgroup of the Q / K apply kernel (8 per thread: the statistics a thread holds are amortised over them)
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 #define LAUNCH_OK() (hipGetLastError() == hipSuccess ? MI355X_OK : MI355X_ELAUNCH)
 
 // Slabs of the token axis: rows per slab (a multiple of SA_RL, at least 64), about 256 (sample, slab) pairs per column tile.  Depends on (B, L) ONLY:

@@ -21,16 +21,9 @@ MI_DEV float div_rn(float a, float b) { return a / b; }
 
 #define LAUNCH_OK() (hipGetLastError() == hipSuccess ? MI355X_OK : MI355X_ELAUNCH)
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline int grid_for(int64_t work, int cap = 4096) {
     int64_t b = (work + 255) / 256;
     return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-// [p, p + bytes) and [q, q + qbytes) share a byte
-inline bool overlap(const void* p, int64_t bytes, const void* q, int64_t qbytes) {
-    if (!p || !q) return false;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return a < b + (uintptr_t)qbytes && b < a + (uintptr_t)bytes;
 }
 
 // MODE 0: one element per thread, any strides.  MODE 1: s_x == 1, a thread writes one 16-byte vector of a tile row.  MODE 2: s_c == 1, a thread writes

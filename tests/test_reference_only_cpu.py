@@ -283,6 +283,7 @@ def test_reference_tree_lowers_to_the_same_program():
 # ------------------------------------------------------------------------------------------------ the native entry point's plumbing
 def test_build_lists_and_header():
     assert "reference_only.hip" in build_native.SOURCES and "../../include/mi355x_refiners_reference_only.h" in build_native.HEADERS
-    assert build_native.DEPS["reference_only.hip"] == ["common.cuh", "../../include/mi355x_refiners_reference_only.h"]
+    assert build_native.DEPS["reference_only.hip"] == ["attn_general_kernel.cuh", "common.cuh", "../../include/mi355x_refiners_reference_only.h"]
+    assert build_native.DEPS["attention_general.hip"] == ["attn_general_kernel.cuh", "common.cuh"]  # (the two share one kernel template)
     fields = [name for name, _t in native.AttnJointArgs._fields_]
     assert fields[:7] == ["dtype", "B", "H", "Lq", "D", "Lk0", "Lk1"] and {"mix", "k1", "vt1", "scale"} <= set(fields)

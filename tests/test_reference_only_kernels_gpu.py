@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from refiners_amd import native
+from tests.attn_general_bits_cases import _vt  # ([B, Lk, C] -> V^T [C, B, Lkp] whose padding columns are finite and NOT zero)
 from tests.kernel_cases import _cmp, _rand
 
 pytestmark = pytest.mark.gpu
@@ -21,18 +22,6 @@ NAN = float("nan")
 H = 2
 LENGTHS = [(16, 16), (64, 64), (100, 37), (256, 256)]
 MIXES = [(0.5, 1.0), (0.0, 1.0), (1.0, 1.0), (0.3, 0.7)]
-
-
-def _pad64(n):
-    return (n + 63) // 64 * 64
-
-
-def _vt(v, junk=3.0):
-    """[B, Lk, C] -> V^T [C, B, Lkp] whose padding columns are finite and NOT zero."""
-    B, Lk, C = v.shape
-    vt = torch.full((C, B, _pad64(Lk)), junk, dtype=v.dtype, device=v.device)
-    vt[:, :, :Lk] = v.permute(2, 0, 1)
-    return vt
 
 
 def _sdpa(q, k, v, D):
@@ -141,6 +130,24 @@ def test_mix_is_read_from_device_memory_at_every_launch():
         mix[0] = value
         native.attention_joint(q, k0, vt0, L0, k1, vt1, L1, out, H, mix=mix)
         _assert_close(out, _model(q, k0, v0, k1, v1, (value, 1.0), D), dtype, f"live mix {value}")
+
+
+def test_bits_are_the_parent_commits():
+    """Every case of tests/attn_general_bits_cases.py (each (QK steps, PV blocks) instance of mi355x_attention_general in float32, bfloat16 with the
+    lazy maximum and bfloat16 without; each instance of mi355x_attention_joint with a snapshot, without one and with segment 1 skipped) writes
+    the bits that the library before the two kernels moved onto one tile loop wrote (tests/golden/attn_general_bits.safetensors), NaN guard
+    rows included.  No tolerance, nothing skipped."""
+    from tests import attn_general_bits_cases as AC
+    from tests.support import golden
+
+    gold = golden(AC.NAME)
+    assert set(gold) == set(AC.CASES) and len(AC.CASES) == 3 * 10 + 2 * 7
+    for case in AC.CASES:
+        got, want = AC.run(native, case), gold[case]
+        assert got.dtype == want.dtype and got.shape == want.shape, case
+        assert torch.isnan(got[:, -1]).all() and not torch.isnan(got[:, :-1]).any(), f"{case}: guard row written, or an output element left unwritten"
+        differ = AC.bits(got) != AC.bits(want)
+        assert torch.equal(AC.bits(got), AC.bits(want)), f"{case}: {int(differ.sum())} of {got.numel()} elements differ"
 
 
 def test_argument_refusals():
