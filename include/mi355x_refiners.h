@@ -286,8 +286,10 @@ int mi355x_attention(const mi355x_attn_args* args, void* stream);
  * so that Q'K'^T = QK^T + bias / scale exactly; then Dqk = 80 + h + w (padded to a multiple of 8 elements) and Dv = 80.
  *
  * Layouts as for mi355x_attention (Q, K, out token-major; V transposed, rows readable and finite up to the next
- * multiple of 64 keys).  Dqk * sizeof(dtype) % 16 == 0, Dv % 4 == 0; supported (Dqk, Dv) up to (64,64), (96,80),
- * (128,80), (160,160), (224,80); anything else returns MI355X_ESHAPE.
+ * multiple of 64 keys).  Dqk * sizeof(dtype) % 16 == 0, Dv % 4 == 0; supported (Dqk, Dv): every pair up to (512,512).  Pairs up to (64,64), (96,80),
+ * (128,80), (160,160), (224,80) run on the instances of csrc/attn_general_kernel.cuh (32 queries per wave, O in one wave's registers); every wider
+ * pair -- the autoencoder's single head of 512 over H * W tokens -- on the wide-head kernel of csrc/attn_wide_kernel.cuh (64 queries per workgroup,
+ * O split over Dv across its four waves), same contract, no score element in HBM.  A width above 512 returns MI355X_ESHAPE.
  */
 typedef struct {
     int32_t dtype;

@@ -8,7 +8,13 @@
 //
 // The kernel, its launcher and the instance table are attn_general_kernel.cuh's (JOINT = false: one key segment; reference_only.hip runs the
 // same loop over two).  This file holds the entry point: argument checks, the parameter block, and the switch between the two bf16 instances.
+// Widths above the instance table, up to (512, 512) -- the autoencoder's single 512-wide head -- go on to mi355x::attention_wide (attn_wide.hip,
+// attn_wide_kernel.cuh): a kernel with a work split of its own behind the same entry point and the same contract.
 #include "attn_general_kernel.cuh"
+
+namespace mi355x {
+int attention_wide(const mi355x_attn_general_args* a, hipStream_t st);  // attn_wide.hip
+}
 
 namespace {
 
@@ -40,5 +46,6 @@ extern "C" int mi355x_attention_general(const mi355x_attn_general_args* a, void*
     p.thr = p.c > 0.f ? 8.0f / p.c : 0.f;
     p.out_scale = a->out_scale;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return a->dtype == MI355X_F32 ? attn_general_dispatch<float, false>(p, st) : attn_general_dispatch<bf16_t, false>(p, st, g_gattn_fast != 0);
+    const int rc = a->dtype == MI355X_F32 ? attn_general_dispatch<float, false>(p, st) : attn_general_dispatch<bf16_t, false>(p, st, g_gattn_fast != 0);
+    return rc == MI355X_ESHAPE ? mi355x::attention_wide(a, st) : rc;  // (no instance covers the widths: the wide kernel, or MI355X_ESHAPE above 512)
 }

@@ -147,7 +147,7 @@ class BlockLowering(Lowering):
             if kind == "flash64":
                 native.attention(q3, out.view(B, Lq, C), heads, st)
                 return out
-            # other head dims (SD1.5: 40 / 80 / 160): one launch per K/V stream, the image-prompt stream is accumulated
+            # other head dims (SD1.5: 40 / 80 / 160; the autoencoder's single head of 512): one launch per K/V stream, the image-prompt stream is accumulated
             for i, (kv, vt3, Lk, osc) in enumerate(st):
                 dst = out if i == 0 else self.pool.get(M, C)
                 native.attention_general(q3, kv, vt3, dst.view(B, Lq, C), heads, Lk, out_scale=osc)
@@ -155,30 +155,8 @@ class BlockLowering(Lowering):
                     native.axpby(out, 1.0, dst, 1.0, out)
                     self.pool.put(dst)
             return out
-        # head dims no flash kernel covers (the VAE's single 512-wide head over H*W tokens): S = Q K^T (float32 scores), row
-        # softmax, O = P V as three native launches per (sample, head) -- the score matrix is 1 GB at 1024x1024 px, nothing
-        # next to 288 GB of HBM, and both GEMMs run at matrix-core speed (K = 512 and K = H*W)
+        # head dims no kernel covers (above 512, or rows that miss the 16-byte rule): torch's SDPA, recorded as a fallback node
         assert v_plain is not None
-        kblk = 128 // self.es
-        if d % kblk == 0 and all(Lk % kblk == 0 and k.shape[0] == B * Lk for (k, _v, Lk, _o) in streams) and len(streams) == 1 and streams[0][3] == 1.0 and self.device.type != "meta":
-            (k, _unused, Lk, osc), v = streams[0], v_plain[0]
-            vt = self.pool.get(B * C, Lk)  # [B][C][Lk]: V^T per sample
-            native.nhwc_to_nchw(v.view(B, Lk, C), vt.view(B, C, Lk, 1), C)
-            scores = self.__dict__.setdefault("_wide_scores", {})
-            if (Lq, Lk) not in scores:
-                scores[(Lq, Lk)] = (torch.empty(Lq, Lk, device=self.device, dtype=torch.float32), torch.empty(Lq, Lk, device=self.device, dtype=self.dtype))
-            sc, pr = scores[(Lq, Lk)]
-            for b in range(B):
-                for hh in range(heads):
-                    qb = q[b * Lq : (b + 1) * Lq, hh * d : (hh + 1) * d]
-                    kb = k[b * Lk : (b + 1) * Lk, hh * d : (hh + 1) * d]
-                    native.gemm([(qb, kb)], sc, out_f32=self.dtype != torch.float32)
-                    native.softmax_rows(sc, pr, Lk, d ** -0.5)
-                    vtb = vt.view(B, C, Lk)[b, hh * d : (hh + 1) * d]
-                    ob = out[b * Lq : (b + 1) * Lq, hh * d : (hh + 1) * d]
-                    native.gemm([(pr, vtb)], ob)
-            self.pool.put(vt)
-            return out
 
         def run() -> None:
             acc = None
@@ -225,11 +203,12 @@ class BlockLowering(Lowering):
         return self.xattn_fold == 2 or native.xattn_tile_ok(M, qspec.N, qspec.K, self.dtype, ln_fused, lora is not None)
 
     def head_kernel(self, d: int) -> Optional[str]:
-        """Which attention kernel serves head dim d: mi355x_attention (64), mi355x_attention_general (<= 160, 16-byte rows), none."""
+        """Which attention kernel serves head dim d: mi355x_attention (64), mi355x_attention_general (<= 512, 16-byte rows: its own instances up to
+        160, the wide-head kernel above), none."""
         if d == 64:
             return "flash64"
         es = 4 if self.dtype == torch.float32 else 2
-        if d <= 160 and (d * es) % 16 == 0 and d % 4 == 0:
+        if d <= 512 and (d * es) % 16 == 0 and d % 4 == 0:
             return "general"
         return None
 

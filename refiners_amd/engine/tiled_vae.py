@@ -146,36 +146,6 @@ class TiledVAELowering(VAEDecoderLowering):
         self.stats["gn_fixed"] = self.stats.get("gn_fixed", 0) + 1
         return oa
 
-    def sdpa(self, q: Tensor, B: int, heads: int, streams: list, v_plain: Optional[list[Tensor]] = None) -> Tensor:
-        """The mid-block's single wide head over a tile whose token count is no multiple of the GEMM's K block (edge tiles: 8 x 7 latents): the
-        base lowering's GEMM / row softmax / GEMM with the key axis zero-padded to the block -- softmax_rows writes zero probabilities into the pad
-        columns, V^T gets zero pad columns from a strided mi355x_vae_tile_gather of V (one launch for the batch)."""
-        M, C = q.shape
-        d, Lq = C // heads, M // B
-        kblk = 128 // self.es
-        plain = self.head_kernel(d) is not None or v_plain is None or len(streams) != 1 or streams[0][3] != 1.0 or d % kblk or self.device.type == "meta"
-        if plain or (streams[0][2] % kblk == 0) or streams[0][0].shape[0] != B * streams[0][2]:
-            return super().sdpa(q, B, heads, streams, v_plain)
-        (k, _vt, Lk, _osc), v = streams[0], v_plain[0]
-        Lp = (Lk + kblk - 1) // kblk * kblk
-        out = self.pool.get(M, C)
-        vt = torch.zeros(B, C, Lp, device=self.device, dtype=self.dtype)  # pad columns stay zero: the gather below never writes them
-        pos_host = native.vae_pos_rows([(b * Lk, 0) for b in range(B)])
-        pos = pos_host.to(self.device)
-        sc = torch.empty(Lq, Lp, device=self.device, dtype=torch.float32)
-        pr = torch.empty(Lq, Lp, device=self.device, dtype=self.dtype)
-        self.keepalive += [vt, pos, pos_host, sc, pr]
-        # V [B * Lk, C] read as a one-channel image: tile b = rows b Lk .. (b + 1) Lk, written transposed (y -> stride 1, x -> stride Lp)
-        native.vae_tile_gather(v.view(1, 1, B * Lk, C), pos, pos_host, vt, B, (Lk, C), (C * Lp, 0, 1, Lp))
-        for b in range(B):
-            for hh in range(heads):
-                qb = q[b * Lq : (b + 1) * Lq, hh * d : (hh + 1) * d]
-                kb = k[b * Lk : (b + 1) * Lk, hh * d : (hh + 1) * d]
-                native.gemm([(qb, kb)], sc[:, :Lk], out_f32=self.dtype != torch.float32)
-                native.softmax_rows(sc, pr, Lk, d ** -0.5)
-                native.gemm([(pr, vt[b, hh * d : (hh + 1) * d])], out[b * Lq : (b + 1) * Lq, hh * d : (hh + 1) * d])
-        return out
-
     def _stages(self, stages: Any, cur: Act, ctx: UNetContext, H: int, W: int, resample: str) -> Act:
         for stage in kids(stages):
             for m in kids(stage):

@@ -6,8 +6,8 @@ into the second conv's K loop, nearest-2x upsampling as address arithmetic):
   latents / encoder_scale -> Conv1x1(4->4)     one tiny NCHW kernel, 1/encoder_scale folded into its weights
   Conv3x3(4->512)                                im2col + GEMM (as the UNet stem)
   15 x Resnet, 3 x Upsample, GN+SiLU+Conv3x3(128->3)   native
-  the mid-block SelfAttention2d (ONE head of 512 over H*W tokens)   q/k/v/out projections native; softmax(QK^T)V itself
-        through torch SDPA: head_dim 512 is outside the flash kernel (listed in stats["fallback_nodes"])
+  the mid-block SelfAttention2d (ONE head of 512 over H*W tokens)   q / k / v^T / out projections native; softmax(QK^T)V is ONE
+        mi355x_attention_general launch for the batch (its wide-head kernel, csrc/attn_wide_kernel.cuh): no score matrix in HBM
 """
 from __future__ import annotations
 
@@ -144,18 +144,46 @@ class VAEDecoderLowering(UNetLowering):
         _expect(isa(gn, "GroupNorm") and len(ch) == 6 and isa(ch[0], "Lambda") and isa(ch[1], "Parallel") and isa(ch[2], "Distribute") and isa(ch[3], "ScaledDotProductAttention")
                 and isa(ch[5], "Lambda") and not ch[3].is_causal, "unexpected SelfAttention2d layout")
         heads = ch[3].num_heads
+        _expect((a.C // heads) != 64, "head_dim 64 SelfAttention2d should use the flash path")
         g = self.groupnorm(a, gn, silu=False)
         q = self.linear(g.t, self.linear_spec(kids(ch[2])[0]))
         k = self.linear(g.t, self.linear_spec(kids(ch[2])[1]))
-        v = self.linear(g.t, self.linear_spec(kids(ch[2])[2]))
-        self.pool.put(g.t)
-        _expect((a.C // heads) != 64, "head_dim 64 SelfAttention2d should use the flash path")
-        o = self.sdpa(q, a.B, heads, [(k, v, a.HW, 1.0)], v_plain=[v])
-        for t in (q, k, v):
+        vs = self.linear_spec(kids(ch[2])[2])
+        if self.head_kernel(a.C // heads) is not None:  # one mi355x_attention_general launch for the batch, V projected straight into V^T
+            vt = self._project_vt_bias(g.t, vs, a.B, a.HW)
+            self.pool.put(g.t)
+            o = self.sdpa(q, a.B, heads, [(k, vt, a.HW, 1.0)])
+            if a.HW % 64 == 0:
+                self.pool.put(vt)
+            released = (q, k)
+        else:  # a width no kernel serves: torch's SDPA on the plain V
+            v = self.linear(g.t, vs)
+            self.pool.put(g.t)
+            o = self.sdpa(q, a.B, heads, [(k, v, a.HW, 1.0)], v_plain=[v])
+            released = (q, k, v)
+        for t in released:
             self.pool.put(t)
         out = self.linear(o, self.linear_spec(ch[4]), res=a.t)
         self.pool.put(o)
         return Act(out, a.B, a.H, a.W)
+
+    def _project_vt_bias(self, h: Tensor, vs: Any, B: int, L: int) -> Tensor:
+        """V^T [C, B * Lp] of h [B * L, Ck] for a value Linear WITH bias (Lp = L rounded up to 64 keys): the GEMM's transposed column group
+        (out_t, nt_begin = 0), which adds the bias per output channel.  As in _project_vt, a token count that is no multiple of 64 takes one
+        launch per sample into a buffer whose pad keys were zeroed once."""
+        if vs.b is None:
+            return self._project_vt(h, vs, B, L, vs.N)
+        _expect(vs.lora is None, "LoRA on the autoencoder's value projection is not supported")
+        if L % 64 == 0:
+            vt = self.pool.get(vs.N, B * L)
+            native.gemm([(h, self.kblocked(vs.w))], None, out_t=vt, nt_begin=0, bias=vs.b)
+            return vt
+        lp = self._pad_keys(L)
+        vt = torch.zeros(vs.N, B * lp, device=self.device, dtype=self.dtype)
+        self.__dict__.setdefault("_keep", []).append(vt)
+        for b in range(B):
+            native.gemm([(h[b * L : (b + 1) * L], self.kblocked(vs.w))], None, out_t=vt[:, b * lp : b * lp + L], nt_begin=0, bias=vs.b)
+        return vt
 
 
 class CompiledVAEDecoder:

@@ -872,8 +872,9 @@ def attention_general(
     causal: bool = False,
     out_scale: float = 1.0,
 ) -> Tensor:
-    """Head shapes other than 64.  q [B, Lq, H*Dqk], k [B, Lk(+), H*Dqk], vt [H*Dv, B, Lkp] (Lkp = Lk rounded up to 64,
-    finite padding), out [B, Lq, H*Dv] -- all views with a contiguous last dimension."""
+    """Head shapes other than 64, up to (Dqk, Dv) = (512, 512): the instances of csrc/attn_general_kernel.cuh up to (160, 160) / (224, 80), the wide-head
+    kernel (csrc/attn_wide_kernel.cuh) above them; NativeError (MI355X_ESHAPE) beyond 512.  q [B, Lq, H*Dqk], k [B, Lk(+), H*Dqk], vt [H*Dv, B, Lkp]
+    (Lkp = Lk rounded up to 64, finite padding), out [B, Lq, H*Dv] -- all views with a contiguous last dimension."""
     a = AttnGeneralArgs()
     B, Lq, HD = q.shape
     assert HD % num_heads == 0 and vt.shape[0] % num_heads == 0 and out.shape[2] == vt.shape[0]
