@@ -19,6 +19,10 @@ from .lowering import Lowering
 from .packing import Act, CatAct, ConvSpec, LinSpec, LoraPack, PackCache, Pool, Unsupported, _expect, cname, isa, kids, launches  # noqa: F401
 
 
+#: REFINERS_AMD_ATTN_STREAMS=0, read once at import: two-stream attentions at the general head dims keep one launch per stream and the axpby (A/B runs)
+ATTN_STREAMS = os.environ.get("REFINERS_AMD_ATTN_STREAMS", "1") != "0"
+
+
 class BlockLowering(Lowering):
     def _split_attention(self, att: Any, allow_causal: bool = False, skip: Any = None) -> tuple[list[Any], Any, Any, Optional[Any]]:
         """Attention | SelfAttention | CrossAttentionAdapter(Attention) -> ([q, k, v nodes], sdpa-like, out node, ip).
@@ -146,6 +150,11 @@ class BlockLowering(Lowering):
             st = self._stream_views(B, C, streams)
             if kind == "flash64":
                 native.attention(q3, out.view(B, Lq, C), heads, st)
+                return out
+            # two short streams at SD1.5's head dims (an IP-Adapter's 77 text + 4 or 16 image keys): one launch, both streams into one accumulator
+            if ATTN_STREAMS and len(st) == 2 and d <= 160 and sum((Lk + 63) // 64 for (_k, _vt, Lk, _osc) in st) <= 3:
+                native.attention_streams(q3, out.view(B, Lq, C), heads, st)
+                self.stats["attn_streams_sites"] = self.stats.get("attn_streams_sites", 0) + 1
                 return out
             # other head dims (SD1.5: 40 / 80 / 160; the autoencoder's single head of 512): one launch per K/V stream, the image-prompt stream is accumulated
             for i, (kv, vt3, Lk, osc) in enumerate(st):

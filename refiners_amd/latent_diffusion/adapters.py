@@ -1,7 +1,7 @@
 """Model-level adapters of the SDXL hot path: IP-Adapter (UNet side), ControlLora, and the LoRA manager.
 
-* ImageProjection / ImageCrossAttention / CrossAttentionAdapter / IPAdapter / SDXLIPAdapter
-      reference latent_diffusion/image_prompt.py:24-45, 237-564 and stable_diffusion_xl/image_prompt.py:9-65
+* ImageProjection / ImageCrossAttention / CrossAttentionAdapter / IPAdapter / SDXLIPAdapter / SD1IPAdapter
+      reference latent_diffusion/image_prompt.py:24-45, 237-564, stable_diffusion_xl/image_prompt.py:9-65 and stable_diffusion_1/image_prompt.py:9-53
 * ConditionEncoder / ZeroConvolution / ControlLora / ControlLoraAdapter
       reference latent_diffusion/stable_diffusion_xl/control_lora.py:14-411
 * SDLoraManager   reference latent_diffusion/lora.py:10-330
@@ -220,6 +220,38 @@ class SDXLIPAdapter(IPAdapter):
                     input_dim=getattr(clip_image_encoder, "embedding_dim", 1280), output_dim=xattn.context_embedding_dim,
                     device=target.device, dtype=target.dtype,
                 )
+        super().__init__(target=target, clip_image_encoder=clip_image_encoder, image_proj=image_proj, scale=scale,
+                         fine_grained=fine_grained, weights=weights)
+
+
+class SD1IPAdapter(IPAdapter):
+    """IP-Adapter on the SD1.5 UNet (reference stable_diffusion_1/image_prompt.py:9-53): image tokens as wide as the UNet's text context (768);
+    fine-grained ("plus"): a PerceiverResampler of 4 layers, 12 heads of 64 and 16 tokens at that width."""
+
+    def __init__(
+        self,
+        target: fl.Chain,
+        clip_image_encoder: Any = None,
+        image_proj: fl.Module | None = None,
+        scale: float = 1.0,
+        fine_grained: bool = False,
+        weights: dict[str, Tensor] | None = None,
+    ) -> None:
+        if image_proj is None:
+            width = target.ensure_find(CrossAttentionBlock2d).context_embedding_dim
+            if not fine_grained:
+                image_proj = ImageProjection(
+                    clip_image_embedding_dim=getattr(clip_image_encoder, "output_dim", 1024),
+                    clip_text_embedding_dim=width, device=target.device, dtype=target.dtype,
+                )
+            else:
+                image_proj = PerceiverResampler(
+                    latents_dim=width, num_attention_layers=4, num_attention_heads=12, head_dim=64, num_tokens=16,
+                    input_dim=getattr(clip_image_encoder, "embedding_dim", 1280), output_dim=width,
+                    device=target.device, dtype=target.dtype,
+                )
+        elif fine_grained:
+            assert isinstance(image_proj, PerceiverResampler)
         super().__init__(target=target, clip_image_encoder=clip_image_encoder, image_proj=image_proj, scale=scale,
                          fine_grained=fine_grained, weights=weights)
 

@@ -10,7 +10,7 @@ scalar constants are read from it at import by refiners_amd.abi, nothing of it i
 Python name of each struct (STRUCT_NAMES), the probing entry points the header leaves out on purpose (UNSTABLE), and the wrappers.
 
 A feature's entry points live in an extension header of their own, include/mi355x_refiners_<feature>.h.  Adding one takes a row in
-ABI_HEADERS here and its source in build_native.SOURCES: the structs, the bound prototypes, the build's dependencies and the header
+ABI_HEADERS (since that list was pinned: ABI_HEADERS_LATER) here and its source in build_native.SOURCES: the structs, the bound prototypes, the build's dependencies and the header
 tests (tests/test_abi_header_cpu.py) all follow from those two.
 """
 from __future__ import annotations
@@ -69,8 +69,13 @@ ABI_HEADERS = [
     ("xattn", "mi355x_refiners_xattn.h", {}),  # a cross-attention folded into its Q projection: it takes the core header's GemmArgs and AttnArgs
     ("sde_step", "mi355x_refiners_sde_step.h", {}),  # the stochastic solver updates (SDE DPM-Solver++)
 ]
+#: headers added after the list above was pinned, row by row, in tests/test_abi_header_cpu.py (that file counts ABI_HEADERS and ALL_EXPORTS):
+#: same row format, read, bound and built the same way
+ABI_HEADERS_LATER = [
+    ("attn_streams", "mi355x_refiners_attn_streams.h", {}),  # short-key attention over one or two K/V streams at the general head widths: it takes the core header's AttnArgs
+]
 #: key -> what refiners_amd.abi read from that header (a name that two headers declare is an import error)
-ABIS = abi.read_all(ABI_HEADERS)
+ABIS = abi.read_all(ABI_HEADERS + ABI_HEADERS_LATER)
 globals().update({cls.__name__: cls for a in ABIS.values() for cls in a.structs.values()})  # GemmSeg ... AttnJointArgs: real ctypes.Structure subclasses
 _abi = ABIS["core"]
 _K = _abi.constants
@@ -78,7 +83,9 @@ _K = _abi.constants
 #: every symbol include/mi355x_refiners.h declares (tests check that the library exports all of them)
 EXPORTS = list(_abi.functions)
 #: every symbol any header declares, in table order: what load() binds and the build checks
-ALL_EXPORTS = [name for a in ABIS.values() for name in a.functions]
+ALL_EXPORTS = [name for key, _file, _names in ABI_HEADERS for name in ABIS[key].functions]
+#: the same for ABI_HEADERS_LATER
+LATER_EXPORTS = [name for key, _file, _names in ABI_HEADERS_LATER for name in ABIS[key].functions]
 #: exported for probing and A/B runs, by design not in the header (no stable contract): name -> (restype, argtypes), applied by load() like the header's
 UNSTABLE = {
     "mi355x_set_option": (C.c_int, [C.c_char_p, C.c_int]),
@@ -848,6 +855,15 @@ def attention_args(q: Optional[Tensor], out: Tensor, num_heads: int, streams: Se
         kv.vt, kv.ldvt, kv.vt_batch_stride = vt.data_ptr(), vt.stride(0), vt.stride(1)
         kv.Lk, kv.out_scale = Lk, osc
     return a, (q, out, tuple(streams))
+
+
+def attention_streams(q: Tensor, out: Tensor, num_heads: int, streams: Sequence[tuple[Tensor, Tensor, int, float]], scale: Optional[float] = None) -> Tensor:
+    """mi355x_attention_streams (csrc/attn_streams.hip): out = sum_s out_scale_s * softmax(scale q k_s^T) v_s in one launch, for head widths up to 160
+    (D * itemsize % 16 == 0) and at most three 64-key tiles over the one or two streams; NativeError (MI355X_ESHAPE) otherwise.  Arguments as for
+    `attention`: q, out [B, Lq, H*D] views; streams (k [B, Lk(+), H*D] view, vt [H*D, B, Lkp] view, Lk, out_scale)."""
+    a, keep = attention_args(q, out, num_heads, streams, scale)
+    _launch("mi355x_attention_streams", (C.byref(a),), "mi355x_attention_streams", keep=keep)
+    return out
 
 
 def xattn_tile_ok(M: int, N: int, K: int, dtype: torch.dtype, ln: bool, lora: bool) -> bool:
