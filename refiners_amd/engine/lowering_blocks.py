@@ -21,6 +21,8 @@ from .packing import Act, CatAct, ConvSpec, LinSpec, LoraPack, PackCache, Pool, 
 
 #: REFINERS_AMD_ATTN_STREAMS=0, read once at import: two-stream attentions at the general head dims keep one launch per stream and the axpby (A/B runs)
 ATTN_STREAMS = os.environ.get("REFINERS_AMD_ATTN_STREAMS", "1") != "0"
+#: REFINERS_AMD_SAG_MASS=0, read once at import: the Self-Attention Guidance tap keeps its GEMM -> softmax -> column-sum chain per (sample, head) (A/B runs)
+SAG_MASS = os.environ.get("REFINERS_AMD_SAG_MASS", "1") != "0"
 
 
 class BlockLowering(Lowering):
@@ -366,13 +368,23 @@ class BlockLowering(Lowering):
     def sag_attention_mass(self, q: Tensor, k: Tensor, B: int, heads: int, L: int, C: int) -> None:
         """Self-Attention Guidance tap (SelfAttentionMap + SAGAdapter.compute_sag_mask, self_attention_guidance.py:22-84): for the
         UNCONDITIONAL half of the CFG batch, mass[b][j] = mean over heads of the attention key j receives from all queries.  The
-        reference materialises softmax(Q K^T / sqrt(d)) for every head and sample; only these column sums are ever used, so per
-        (sample, head): scores GEMM (float32) -> row softmax -> column sum, three small launches on an L x L scratch."""
+        reference materialises softmax(Q K^T / sqrt(d)) for every head and sample; only these column sums are ever used.  ONE
+        mi355x_attention_key_mass call (two launches, the scores in registers only) at the head widths it takes.  Any other width, and
+        REFINERS_AMD_SAG_MASS=0, takes the chain per (sample, head): scores GEMM (float32) -> row softmax -> column sum, three small
+        launches on an L x L scratch; the chain needs the GEMM's K granularity of the head width."""
         d = C // heads
-        kblk = 128 // self.es
-        _expect(d % kblk == 0 and B % 2 == 0, "self-attention guidance tap: head width / batch not supported")
+        _expect(B % 2 == 0, "self-attention guidance tap: batch not supported")
         n = B // 2
         mass = torch.zeros(n, L, device=self.device, dtype=torch.float32)
+        self.sag = {"mass": mass, "tokens": L}
+        if SAG_MASS and native.key_mass_ok(d, self.dtype):
+            lse = torch.empty(n, heads, L, device=self.device, dtype=torch.float32)
+            self.__dict__.setdefault("_keep", []).extend([mass, lse])
+            if self.device.type != "meta":
+                native.attention_key_mass(q.view(B, L, C)[:n], k.view(B, L, C)[:n], heads, d ** -0.5, lse, mass)
+            self.stats["sag_mass_fused"] = True
+            return
+        _expect(d % (128 // self.es) == 0, "self-attention guidance tap: head width not supported")
         sc = torch.empty(L, L, device=self.device, dtype=torch.float32)
         pr = torch.empty(L, L, device=self.device, dtype=self.dtype)
         self.__dict__.setdefault("_keep", []).extend([mass, sc, pr])
@@ -383,7 +395,6 @@ class BlockLowering(Lowering):
                     native.gemm([(qb, kb)], sc, out_f32=self.dtype != torch.float32)
                     native.softmax_rows(sc, pr, L, d ** -0.5)
                     native.colsum_rows(pr, mass[b], accumulate=h > 0, scale=1.0 / heads)
-        self.sag = {"mass": mass, "tokens": L}
 
     def cross_attention(self, x: Tensor, B: int, ln: Any, par: Any, att: Any, ctx: "UNetContext", stats: Optional[Tensor] = None,
                         stats_out: Optional[Tensor] = None) -> Tensor:

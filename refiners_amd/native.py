@@ -73,6 +73,7 @@ ABI_HEADERS = [
 #: same row format, read, bound and built the same way
 ABI_HEADERS_LATER = [
     ("attn_streams", "mi355x_refiners_attn_streams.h", {}),  # short-key attention over one or two K/V streams at the general head widths: it takes the core header's AttnArgs
+    ("key_mass", "mi355x_refiners_key_mass.h", {"mi355x_key_mass_args": "KeyMassArgs"}),  # the attention mass per key (the SAG tap), no attention matrix in memory
 ]
 #: key -> what refiners_amd.abi read from that header (a name that two headers declare is an import error)
 ABIS = abi.read_all(ABI_HEADERS + ABI_HEADERS_LATER)
@@ -94,6 +95,7 @@ UNSTABLE = {
     "mi355x_attention_set_nw": (C.c_int, [C.c_int]),
     "mi355x_attention_set_pipeline": (C.c_int, [C.c_int, C.c_int]),
     "mi355x_attention_general_set_fast": (C.c_int, [C.c_int]),
+    "mi355x_key_mass_set_tile": (C.c_int, [C.c_int]),
 }
 
 ABI_VERSION = _K["MI355X_ABI_VERSION"]
@@ -864,6 +866,26 @@ def attention_streams(q: Tensor, out: Tensor, num_heads: int, streams: Sequence[
     a, keep = attention_args(q, out, num_heads, streams, scale)
     _launch("mi355x_attention_streams", (C.byref(a),), "mi355x_attention_streams", keep=keep)
     return out
+
+
+def key_mass_ok(head_dim: int, dtype: torch.dtype) -> bool:
+    """The head widths mi355x_attention_key_mass takes: rows of whole 16-byte chunks, at most 160 columns."""
+    return head_dim <= 160 and (head_dim * dtype.itemsize) % 16 == 0
+
+
+def attention_key_mass(q: Tensor, k: Tensor, num_heads: int, scale: Optional[float], lse: Tensor, mass: Tensor) -> Tensor:
+    """mi355x_attention_key_mass (csrc/attn_key_mass.hip): mass[b, j] = mean over heads, sum over queries of softmax_j(scale q k^T), two launches and no
+    L x L matrix in memory.  q, k: [B, L, H*D] views (last dim contiguous; column slices of one buffer are fine); lse: float32 [B, H, >= L] scratch;
+    mass: float32 [B, >= L], columns 0 .. L-1 written.  NativeError (MI355X_ESHAPE) for D > 160, D * itemsize % 16 != 0 or a broken alignment rule."""
+    B, L, HD = q.shape
+    assert tuple(k.shape) == (B, L, HD) and q.stride(2) == 1 and k.stride(2) == 1 and q.dtype == k.dtype and HD % num_heads == 0
+    assert lse.dtype == torch.float32 and mass.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape[:2]) == (B, num_heads) and mass.shape[0] == B and mass.stride(1) == 1
+    a = KeyMassArgs()
+    a.dtype, a.B, a.H, a.L, a.D = dtype_code(q.dtype), B, num_heads, L, HD // num_heads
+    a.scale = scale if scale is not None else a.D ** -0.5
+    _launch("mi355x_attention_key_mass", (C.byref(a), q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0), lse.data_ptr(), lse.shape[2],
+                                          mass.data_ptr(), mass.stride(0)), "mi355x_attention_key_mass", keep=(a, q, k, lse, mass))
+    return mass
 
 
 def xattn_tile_ok(M: int, N: int, K: int, dtype: torch.dtype, ln: bool, lora: bool) -> bool:
