@@ -18,7 +18,8 @@ reference's own convention for unknown children -- the stock child loop runs (fl
 "unsupported => fall back, never error") -- at two levels, both reported: a context-free sub-tree inside a UNet stage runs through its own
 torch forward inside the recorded program (`.stats["fallback_nodes"]`); anything else (a node that needs the Chain's context store at run
 time, an unknown top-level layout) makes the WHOLE call run `unet(x)`, with a `RuntimeWarning` naming the reason and
-`.stats["whole_fallback"]` set.  Adapters outside SURVEY.md section 8 (FreeU ...) therefore keep working, unfused.
+`.stats["whole_fallback"]` set.  Adapters outside SURVEY.md section 8 therefore keep working, unfused -- SDFreeUAdapter among them unless
+REFINERS_AMD_FREEU=1 is set when the tree is lowered: then its concatenators are one native launch each (`.stats["freeu_sites"]`).
 StyleAlignedAdapter is lowered (`.stats["style_aligned_sites"]`): its scale lives in device memory and is refreshed before every replay.
 """
 from __future__ import annotations
@@ -273,6 +274,8 @@ class CompiledUNet:
                 sig.append(float(m.scale))
             if isa(m, "Controlnet"):
                 sig.extend([float(m.scale), float(m.scale_decay)])
+            if isa(m, "FreeUBackboneFeatures"):  # (the skip scale lives in a closure of its node: a new scale is a new node)
+                sig.append(float(m.backbone_scale))
         return hash(tuple(sig))
 
     def prepare_explicit(self, x_shape: tuple, device: torch.device, got: dict[str, Any]) -> bool:

@@ -558,6 +558,7 @@ class BlockLowering(Lowering):
         self.pool.put(g2.t)
         if isinstance(src, CatAct):  # the block consumed the concatenation: its first part goes back to the pool (the skip stays pinned) ...
             self.pool.put(src.a.t)
+            self.pool.put(src.b.t)   # (a no-op for a pinned skip slot; FreeU's filtered copy of one goes back)
             if a is not src:         # ... and so does the materialised copy, where one had to be made
                 self.pool.put(a.t)
         return out

@@ -358,6 +358,7 @@ class UNetLowering(ReferenceOnlyLowering, EllaLowering, BlockLowering):
             cat = cur
             cur = self.materialise(cat)
             self.pool.put(cat.a.t)
+            self.pool.put(cat.b.t)  # (a pinned skip slot stays where it is; FreeU's filtered copy goes back)
             self.stats["concat_materialised"] = self.stats.get("concat_materialised", 0) + 1
         if isa(m, "ResidualBlock"):
             out = self.residual_block(m, cur, ctx)
@@ -392,6 +393,8 @@ class UNetLowering(ReferenceOnlyLowering, EllaLowering, BlockLowering):
             skip = self.slot(ctx, m.n)
             _expect(skip is not None and (skip.B, skip.H, skip.W) == (cur.B, cur.H, cur.W), "skip tensor missing or of another size")
             return CatAct(cur, skip)  # (cur is released by the ResidualBlock that consumes the pair)
+        elif isa(m, "FreeUResidualConcatenator") and os.environ.get("REFINERS_AMD_FREEU", "0") not in ("", "0"):
+            return self.freeu_concatenator(m, cur, ctx)
         elif isa(m, "ZeroConvolution"):
             self.zero_convolution(m, cur, ctx)
             return cur
@@ -409,6 +412,32 @@ class UNetLowering(ReferenceOnlyLowering, EllaLowering, BlockLowering):
 
     def slot(self, ctx: UNetContext, n: int) -> Optional[Act]:
         return ctx.residuals[n]
+
+    def freeu_concatenator(self, m: Any, cur: Act, ctx: UNetContext) -> CatAct:
+        """FreeUResidualConcatenator = Concatenate(FreeUBackboneFeatures, FreeUSkipFeatures(UseContext unet.residuals -> [n], Lambda), dim=1)
+        (latent_diffusion/freeu.py:44-70): ONE mi355x_freeu_filter launch scales the first half of `cur` in place (as the reference does) and writes
+        the Fourier-filtered skip, as a low-rank update from engine.freeu's tables, into a buffer of its own; the pair goes on as a CatAct like a
+        plain ResidualConcatenator's.  Neither part is what its producer's epilogue summarised any more, so both go on WITHOUT column statistics
+        and the two-source GroupNorm runs its own statistics pass.  Opt-in (REFINERS_AMD_FREEU=1, read here, while the tree is lowered): unset, the
+        node is refused like any other that reads the context store.  `backbone_scale` and the skip scale are read NOW and baked into the launch
+        and its tables; they are part of the tree state (CompiledUNet._tree_state), so changing one lowers the tree again."""
+        from . import freeu
+
+        ch = kids(m)
+        _expect(len(ch) == 2 and isa(ch[0], "FreeUBackboneFeatures") and isa(ch[1], "FreeUSkipFeatures") and m.dim == 1, "unexpected FreeUResidualConcatenator layout")
+        sk = kids(ch[1])
+        _expect(len(sk) == 2 and self._reads_residuals(sk[0]) and isa(sk[1], "Lambda"), "unexpected FreeUSkipFeatures layout")
+        n = sk[0].func(list(range(len(ctx.residuals))))  # (the slot index lives in the reader's closure: ask it)
+        _expect(isinstance(n, int), "FreeUSkipFeatures does not pick one residual slot")
+        skip = self.slot(ctx, n)
+        _expect(skip is not None and (skip.B, skip.H, skip.W) == (cur.B, cur.H, cur.W), "skip tensor missing or of another size")
+        _expect(not any(r is not None and r.t is cur.t for r in ctx.residuals), "the backbone features are a residual slot: they cannot be scaled in place")
+        _expect(skip.C % 8 == 0 and cur.C % 16 == 0, "FreeU channel counts are not multiples of 8 (skip) and 16 (backbone)")
+        analysis, synthesis, rank = freeu.tables(skip.H, skip.W, freeu.probe_skip_scale(sk[1].func), 1, self.cache, self.device)
+        out = self.pool.get(skip.M, skip.C)
+        native.freeu_filter(skip.t, out, cur.t, cur.B, analysis, synthesis, rank, float(ch[0].backbone_scale))
+        self.stats["freeu_sites"] = self.stats.get("freeu_sites", 0) + 1
+        return CatAct(Act(cur.t, cur.B, cur.H, cur.W), Act(out, skip.B, skip.H, skip.W))
 
     def accumulate(self, ctx: UNetContext, n: int, a: Act) -> None:
         """residuals[n] <- a + residuals[n]   (unet.py:54-66); aliasing `a` when the slot still holds its initial 0.0."""

@@ -74,6 +74,7 @@ ABI_HEADERS = [
 ABI_HEADERS_LATER = [
     ("attn_streams", "mi355x_refiners_attn_streams.h", {}),  # short-key attention over one or two K/V streams at the general head widths: it takes the core header's AttnArgs
     ("key_mass", "mi355x_refiners_key_mass.h", {"mi355x_key_mass_args": "KeyMassArgs"}),  # the attention mass per key (the SAG tap), no attention matrix in memory
+    ("freeu", "mi355x_refiners_freeu.h", {"mi355x_freeu_args": "FreeuArgs"}),  # FreeU's residual concatenator: the Fourier skip filter as a low-rank update, the scaled backbone half
 ]
 #: key -> what refiners_amd.abi read from that header (a name that two headers declare is an import error)
 ABIS = abi.read_all(ABI_HEADERS + ABI_HEADERS_LATER)
@@ -96,6 +97,7 @@ UNSTABLE = {
     "mi355x_attention_set_pipeline": (C.c_int, [C.c_int, C.c_int]),
     "mi355x_attention_general_set_fast": (C.c_int, [C.c_int]),
     "mi355x_key_mass_set_tile": (C.c_int, [C.c_int]),
+    "mi355x_freeu_set_slab": (C.c_int, [C.c_int]),
 }
 
 ABI_VERSION = _K["MI355X_ABI_VERSION"]
@@ -886,6 +888,24 @@ def attention_key_mass(q: Tensor, k: Tensor, num_heads: int, scale: Optional[flo
     _launch("mi355x_attention_key_mass", (C.byref(a), q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0), lse.data_ptr(), lse.shape[2],
                                           mass.data_ptr(), mass.stride(0)), "mi355x_attention_key_mass", keep=(a, q, k, lse, mass))
     return mass
+
+
+def freeu_filter(skip: Tensor, skip_out: Tensor, backbone: Tensor, images: int, analysis: Tensor, synthesis: Tensor, rank: int, backbone_scale: float) -> Tensor:
+    """mi355x_freeu_filter (csrc/freeu.hip): FreeU's residual concatenator in one launch.  skip, skip_out: [images * HW, C] token rows (last dim
+    contiguous); per image skip_out = skip + synthesis^T (analysis skip), the Fourier filter as engine.freeu.tables factors it.  backbone:
+    [images * HW, C_b] token rows, columns 0 .. C_b / 2 - 1 multiplied by backbone_scale in place, the others untouched.  analysis, synthesis: float32
+    [16, HWpad] (HWpad a multiple of 128, zeros in rows >= rank and columns >= HW).  NativeError (MI355X_ESHAPE) for C % 8 != 0 or (C_b / 2) % 8 != 0."""
+    rows, width = skip.shape
+    assert tuple(skip_out.shape) == (rows, width) and backbone.shape[0] == rows and rows % images == 0 and skip.dtype == skip_out.dtype == backbone.dtype
+    assert skip.stride(1) == 1 and skip_out.stride(1) == 1 and backbone.stride(1) == 1
+    assert analysis.dtype == torch.float32 and synthesis.dtype == torch.float32 and analysis.is_contiguous() and synthesis.is_contiguous()
+    assert analysis.shape == synthesis.shape and analysis.shape[0] == 16
+    a = FreeuArgs()
+    a.dtype, a.B, a.HW, a.C_skip, a.C_b, a.R = dtype_code(skip.dtype), images, rows // images, width, backbone.shape[1], rank
+    a.backbone_scale = backbone_scale
+    _launch("mi355x_freeu_filter", (C.byref(a), skip.data_ptr(), skip.stride(0), skip_out.data_ptr(), skip_out.stride(0), backbone.data_ptr(), backbone.stride(0),
+                                    analysis.data_ptr(), synthesis.data_ptr(), analysis.shape[1]), "mi355x_freeu_filter", keep=(a, skip, skip_out, backbone, analysis, synthesis))
+    return skip_out
 
 
 def xattn_tile_ok(M: int, N: int, K: int, dtype: torch.dtype, ln: bool, lora: bool) -> bool:
