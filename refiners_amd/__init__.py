@@ -11,11 +11,12 @@ def namespace():
     from .latent_diffusion.multi_diffusion import (DiffusionTarget, MultiDiffusion, SD1DiffusionTarget, SD1MultiDiffusion, SDXLMultiDiffusion, SDXLTarget, Size,
                                                    Tile)
     from .latent_diffusion.style_aligned import StyleAlignedAdapter
+    from .latent_diffusion.t2i import SD1T2IAdapter, SDXLT2IAdapter
 
     return SimpleNamespace(fl=fl, LinearLora=LinearLora, Conv2dLora=Conv2dLora, LoraAdapter=LoraAdapter, SDXLIPAdapter=SDXLIPAdapter, SD1IPAdapter=SD1IPAdapter,
                            ControlLoraAdapter=ControlLoraAdapter, ConditionEncoder=ConditionEncoder, ZeroConvolution=ZeroConvolution, StyleAlignedAdapter=StyleAlignedAdapter,
                            Tile=Tile, Size=Size, DiffusionTarget=DiffusionTarget, MultiDiffusion=MultiDiffusion, SDXLTarget=SDXLTarget,
-                           SDXLMultiDiffusion=SDXLMultiDiffusion, SD1DiffusionTarget=SD1DiffusionTarget, SD1MultiDiffusion=SD1MultiDiffusion)
+                           SDXLMultiDiffusion=SDXLMultiDiffusion, SD1DiffusionTarget=SD1DiffusionTarget, SD1MultiDiffusion=SD1MultiDiffusion, SD1T2IAdapter=SD1T2IAdapter, SDXLT2IAdapter=SDXLT2IAdapter)
 
 
 def __getattr__(name: str):

@@ -5,4 +5,8 @@ def __getattr__(name: str):
         from .ella import CompiledELLA
 
         return CompiledELLA
+    if name == "CompiledT2IConditionEncoder":
+        from .t2i import CompiledT2IConditionEncoder
+
+        return CompiledT2IConditionEncoder
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,9 +1,10 @@
 """Host-side mirror of refiners' T2I-Adapter (`foundationals/latent_diffusion/t2i_adapter.py:20-220`,
-`stable_diffusion_xl/t2i_adapter.py:9-49`) -- SURVEY.md section 8(f) next-4.
+`stable_diffusion_xl/t2i_adapter.py:9-49`, `stable_diffusion_1/t2i_adapter.py:9-41`) -- SURVEY.md section 8(f) next-4.
 
 Two halves with very different costs:
   * `ConditionEncoderXL`: a small conv net that turns the conditioning picture (depth, canny, ...) into four feature maps,
-    ONCE per image (`compute_condition_features`); it stays on torch.
+    ONCE per image (`compute_condition_features`); `refiners_amd.engine.CompiledT2IConditionEncoder(adapter.condition_encoder)` runs it as one
+    native program (pixel-unshuffle stem, implicit-GEMM blocks) and returns the same tuple.
   * `T2IFeatures`: four `x + scale * features[i]` nodes inside the UNet (three down blocks and the middle block), hit on
     EVERY denoising step; the engine lowers them to one fused add each (refiners_amd/engine/unet_lowering.py).
 State-dict keys of the encoder equal the reference's (tests/golden/t2i_keys.json).
@@ -179,4 +180,28 @@ class SDXLT2IAdapter(T2IAdapter):
         for n, feat in zip(self.residual_indices, self._features):
             self.target.layer(("DownBlocks", n), fl.Chain).remove(feat)
         self.target.layer("MiddleBlock", fl.Chain).remove(self._features[-1])
+        super().eject()
+
+
+class SD1T2IAdapter(T2IAdapter):
+    """Features 0..3 go in front of the ResidualAccumulator of DownBlocks 2 / 5 / 8 / 11 (`stable_diffusion_1/t2i_adapter.py:9-41`)."""
+
+    def __init__(self, target: fl.Chain, name: str, condition_encoder: Optional[ConditionEncoder] = None, scale: float = 1.0,
+                 weights: Optional[dict[str, Tensor]] = None) -> None:
+        self.residual_indices = (2, 5, 8, 11)
+        self._features = [T2IFeatures(name=name, index=i, scale=scale) for i in range(4)]
+        super().__init__(target=target, name=name, condition_encoder=condition_encoder or ConditionEncoder(device=target.device, dtype=target.dtype),
+                         weights=weights)
+
+    def inject(self, parent: Optional[fl.Chain] = None) -> "SD1T2IAdapter":
+        for n, feat in zip(self.residual_indices, self._features):
+            block = self.target.layer(("DownBlocks", n), fl.Chain)
+            for layer in block.layers(T2IFeatures):
+                assert layer.name != self.name, f"T2I-Adapter named {self.name} is already injected"
+            block.insert_before_type(ResidualAccumulator, feat)
+        return super().inject(parent)  # type: ignore[return-value]
+
+    def eject(self) -> None:
+        for n, feat in zip(self.residual_indices, self._features):
+            self.target.layer(("DownBlocks", n), fl.Chain).remove(feat)
         super().eject()

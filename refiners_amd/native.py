@@ -75,6 +75,7 @@ ABI_HEADERS_LATER = [
     ("attn_streams", "mi355x_refiners_attn_streams.h", {}),  # short-key attention over one or two K/V streams at the general head widths: it takes the core header's AttnArgs
     ("key_mass", "mi355x_refiners_key_mass.h", {"mi355x_key_mass_args": "KeyMassArgs"}),  # the attention mass per key (the SAG tap), no attention matrix in memory
     ("freeu", "mi355x_refiners_freeu.h", {"mi355x_freeu_args": "FreeuArgs"}),  # FreeU's residual concatenator: the Fourier skip filter as a low-rank update, the scaled backbone half
+    ("t2i", "mi355x_refiners_t2i.h", {"mi355x_t2i_stem_args": "T2iStemArgs", "mi355x_t2i_pool_args": "T2iPoolArgs"}),  # the T2I-Adapter condition encoder: pixel-unshuffle stem, 2 x 2 average pool
 ]
 #: key -> what refiners_amd.abi read from that header (a name that two headers declare is an import error)
 ABIS = abi.read_all(ABI_HEADERS + ABI_HEADERS_LATER)
@@ -98,6 +99,7 @@ UNSTABLE = {
     "mi355x_attention_general_set_fast": (C.c_int, [C.c_int]),
     "mi355x_key_mass_set_tile": (C.c_int, [C.c_int]),
     "mi355x_freeu_set_slab": (C.c_int, [C.c_int]),
+    "mi355x_t2i_set_strip": (C.c_int, [C.c_int, C.c_int]),
 }
 
 ABI_VERSION = _K["MI355X_ABI_VERSION"]
@@ -614,8 +616,9 @@ def conv_gemm(
     colstats_out: Optional[Tensor] = None,
     table_may_replace_split: bool = False,
     gelu: bool = False,
+    relu: bool = False,
 ) -> Tensor:
-    """Implicit-GEMM convolution over NHWC images.  gelu: the erf-GELU epilogue (geglu = 2), not combinable with ksplit.
+    """Implicit-GEMM convolution over NHWC images.  gelu / relu: the erf-GELU (geglu = 2) / ReLU (geglu = 4) epilogue, not combinable with ksplit.
 
     segs: (image [B,H,W,C] NHWC-contiguous or channel-sliced view, packed weight [N, ksize*ksize*C], ksize, stride, ups).
     out: [B*OH*OW, N] rows (i.e. NHWC output).
@@ -641,8 +644,8 @@ def conv_gemm(
         sg.ksize, sg.stride, sg.ups, sg.H, sg.W, sg.asym = ksize, stride, ups, h, wd, asym
         sg.kblocked = 1 if isinstance(w, KBlocked) else 0
     a.zeros = zero_page(img0.device).data_ptr()
-    assert not (gelu and ksplit > 1)
-    _fill_epilogue(a, out, bias, rowbias, rows_per_group, res, 2 if gelu else False)
+    assert not ((gelu or relu) and ksplit > 1) and not (gelu and relu)
+    _fill_epilogue(a, out, bias, rowbias, rows_per_group, res, 2 if gelu else (4 if relu else False))
     keep: list = []
     if lora is not None:
         _lora_fill(a, lora, False, img0.dtype, tuple(w0.shape)[1], keep, lora_sync)
@@ -906,6 +909,44 @@ def freeu_filter(skip: Tensor, skip_out: Tensor, backbone: Tensor, images: int, 
     _launch("mi355x_freeu_filter", (C.byref(a), skip.data_ptr(), skip.stride(0), skip_out.data_ptr(), skip_out.stride(0), backbone.data_ptr(), backbone.stride(0),
                                     analysis.data_ptr(), synthesis.data_ptr(), analysis.shape[1]), "mi355x_freeu_filter", keep=(a, skip, skip_out, backbone, analysis, synthesis))
     return skip_out
+
+
+def t2i_pack_stem(w: Tensor, r: int, dtype: torch.dtype) -> Tensor:
+    """The weight [C0, cin r^2, 3, 3] of the convolution behind PixelUnshuffle(r) (unshuffled channel c r^2 + dy r + dx) -> mi355x_t2i_stem's operand:
+    K re-ordered to (c, ky, dy, kx, dx), so that the (kx, dx) of one (c, ky, dy) are one run of a picture row, then cut into 16-byte chunks of K
+    and stored chunk-major, [K / E, C0, E] with E = 16 / itemsize of `dtype`."""
+    C0, cu, kh, kw = w.shape
+    assert (kh, kw) == (3, 3) and cu % (r * r) == 0
+    e = 16 // torch.empty((), dtype=dtype).element_size()
+    k = w.detach().to(dtype).reshape(C0, cu // (r * r), r, r, 3, 3).permute(0, 1, 4, 2, 5, 3).reshape(C0, -1)  # (n | c, ky, dy, kx, dx)
+    return k.reshape(C0, -1, e).permute(1, 0, 2).contiguous()
+
+
+def t2i_stem(picture: Tensor, weight: Tensor, bias: Optional[Tensor], out: Tensor, r: int) -> Tensor:
+    """mi355x_t2i_stem (csrc/t2i.hip): Conv2d(cin r^2 -> C0, 3, padding 1)(PixelUnshuffle(r)(picture)) as channels-last rows, the unshuffled tensor never
+    written.  picture: [B, cin, r h, r w] contiguous, float32 or bfloat16 (cin 1 or 3, r 8 or 16); weight: t2i_pack_stem(conv.weight, r, out.dtype);
+    bias: [C0] of out's dtype or None; out: [B h w, C0] rows (last dim contiguous), whose dtype is the compute dtype.  NativeError (MI355X_ESHAPE)
+    for another r or cin or C0 % 16 != 0."""
+    B, cin, Hp, Wp = picture.shape
+    C0 = out.shape[1]
+    assert picture.is_contiguous() and Hp % r == 0 and Wp % r == 0 and out.stride(1) == 1 and out.shape[0] == B * (Hp // r) * (Wp // r)
+    assert weight.dtype == out.dtype and weight.is_contiguous() and weight.numel() == C0 * cin * 9 * r * r and weight.shape[1] == C0
+    assert bias is None or (bias.dtype == out.dtype and bias.is_contiguous() and bias.numel() == C0)
+    a = T2iStemArgs()
+    a.dtype, a.pic_dtype, a.B, a.cin, a.r, a.h, a.w, a.C0 = dtype_code(out.dtype), dtype_code(picture.dtype), B, cin, r, Hp // r, Wp // r, C0
+    _launch("mi355x_t2i_stem", (C.byref(a), picture.data_ptr(), weight.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(), out.stride(0)),
+            "mi355x_t2i_stem", keep=(a, picture, weight, bias, out))
+    return out
+
+
+def t2i_pool(x: Tensor, B: int, H: int, W: int, out: Tensor) -> Tensor:
+    """mi355x_t2i_pool: AvgPool2d(2, 2) on channels-last rows, x [B H W, C] -> out [B (H // 2) (W // 2), C] (odd sizes floored, float32 sum)."""
+    assert x.shape[0] == B * H * W and out.shape[0] == B * (H // 2) * (W // 2) and x.shape[1] == out.shape[1] and x.dtype == out.dtype
+    assert x.stride(1) == 1 and out.stride(1) == 1
+    a = T2iPoolArgs()
+    a.dtype, a.B, a.H, a.W, a.C = dtype_code(x.dtype), B, H, W, x.shape[1]
+    _launch("mi355x_t2i_pool", (C.byref(a), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0)), "mi355x_t2i_pool", keep=(a, x, out))
+    return out
 
 
 def xattn_tile_ok(M: int, N: int, K: int, dtype: torch.dtype, ln: bool, lora: bool) -> bool:
