@@ -35,6 +35,7 @@ from torch import Tensor
 from .. import native
 from ..fluxion.tree import tree_epoch
 from .packing import PackCache, Unsupported, isa, kids, launches  # noqa: F401
+from .program import Program  # noqa: F401
 from .unet_lowering import UNetIO, UNetLowering  # noqa: F401
 
 TOKEN_CONTEXTS = (("cross_attention_block", "clip_text_embedding"), ("ip_adapter", "clip_image_embedding"), ("adapted_cross_attention_block", "llm_text_embedding"))
@@ -57,36 +58,6 @@ def _weights_version(unet: Any, cache: Optional[dict] = None, epoch: Any = None)
     if cache.get("epoch") != epoch:
         cache["epoch"], cache["params"] = epoch, list(unet.parameters())
     return sum(p._version for p in cache["params"])
-
-
-class Program:
-    """A lowered launch list replayed directly the first time and as ONE HIP graph afterwards (every buffer is static)."""
-
-    def __init__(self, ops: list, use_graph: bool, weight_prefetch: Optional[bool] = None, low: Any = None) -> None:
-        # `low`: the Lowering the launches came from.  Given, every run ends with a look at its hand-over error words (in-launch LoRA, stream-K):
-        # these programs -- text / image encoders, SAM -- run once per prompt or picture and their callers read the result next, so the host
-        # round trip costs nothing that is not paid anyway
-        self.ops, self.use_graph, self.low = ops, use_graph, low
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        if weight_prefetch is None:
-            weight_prefetch = os.environ.get("REFINERS_AMD_WEIGHT_PREFETCH", "1") != "0"
-        self.prefetch = native.link_weight_prefetch(ops, enable=weight_prefetch)  # every GEMM pulls the next one's weights into the Infinity Cache
-
-    def run(self) -> None:
-        if self.use_graph and self.graph is not None:
-            self.graph.replay()
-        else:
-            native.replay(self.ops)  # also the warm-up: first-launch work (function attributes) must not be captured
-            if self.use_graph:
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    native.replay(self.ops)
-                self.graph = g
-        if self.low is not None:
-            bad = self.low.handover_pending()
-            if bad and bool((bad[0] if len(bad) == 1 else torch.stack(bad).any()).item()):
-                self.low.handover_raise()
 
 
 class CompiledUNet:

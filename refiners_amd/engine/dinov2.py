@@ -27,7 +27,6 @@ the GEMM K block, LoRA on a Linear, inputs smaller than one patch.
 from __future__ import annotations
 
 import math
-import warnings
 from typing import Any, Optional
 
 import numpy as np
@@ -36,12 +35,11 @@ from torch import Tensor
 
 from .. import native
 from ..fluxion.tree import tree_epoch
-from .compiled import Program
 from .lowering_blocks import BlockLowering as Lowering
-from .packing import LinSpec, PackCache, Unsupported, _expect, cname, isa, kids, launches
+from .packing import LinSpec, PackCache, _expect, cname, isa, kids, launches
+from .program import MAX_PROGRAMS, Entry, HasPrograms, ProgramCache
 
 MODES = ("bicubic", "bilinear")
-MAX_PROGRAMS = 8  # lowered shapes kept per CompiledDINOv2
 
 
 # ------------------------------------------------------------------------------------------------ tap tables (host, float64)
@@ -321,31 +319,18 @@ class DINOv2Lowering(Lowering):
         return buf
 
 
-class _Entry:
-    """One lowered shape: its static input / output buffers, lowering and program."""
-
-    def __init__(self, x: Tensor, out: Tensor, low: DINOv2Lowering, program: Program) -> None:
-        self.x, self.out, self.low, self.program = x, out, low, program
-
-
-class CompiledDINOv2:
+class CompiledDINOv2(HasPrograms):
     """`fast = CompiledDINOv2(model); y = fast(images)` == `model(images)`: [B, 3, H, W] -> [B, 1 + registers + (H // p) (W // p), D].
-    One lowered program and one HIP graph per (B, H, W), the last MAX_PROGRAMS shapes kept: a repeat call of a shape replays its graph.
-    `dtype` (default: the tree's) is the compute dtype.  An in-place edit of a weight re-lowers (only what changed is re-packed).  A tree the
-    lowering does not cover runs its stock forward behind a RuntimeWarning."""
+    One lowered program and one HIP graph per (B, H, W), the last MAX_PROGRAMS shapes kept.  `dtype` (default: the tree's) is the compute
+    dtype.  A tree the lowering does not cover runs its stock forward behind a RuntimeWarning."""
 
     def __init__(self, model: Any, dtype: Optional[torch.dtype] = None, use_graph: bool = True) -> None:
         native.load()
         self.model = model
         self.dtype = dtype
         self.use_graph = use_graph
-        self.cache = PackCache()
-        self.entries: dict[Any, _Entry] = {}
-        self.version: Any = None
-        self.bad_keys: set = set()
-        self.lowerings = 0
+        self.programs = ProgramCache("CompiledDINOv2", MAX_PROGRAMS, fallback=True)
         self.stats: dict[str, Any] = {}
-        self.program: Optional[Program] = None
 
     def _tree_dtype(self) -> torch.dtype:
         return next(p.dtype for p in self.model.parameters())
@@ -358,41 +343,22 @@ class CompiledDINOv2:
     @torch.no_grad()
     def __call__(self, image: Tensor) -> Tensor:
         dtype = self.dtype or self._tree_dtype()
-        version = self._weights_version()
-        edited = version != self.version
-        if edited:  # every program goes; the first lowering after it sweeps the packs nothing uses any more
-            self.entries.clear()
-            self.bad_keys.clear()
-            self.cache.used.clear()
-            self.version = version
-        key = (tuple(image.shape), dtype, image.device)
-        if key in self.bad_keys:
-            return self._stock(image)
-        e = self.entries.get(key)
+
+        def build(cache: PackCache) -> Entry:
+            _expect(image.dim() == 4, f"input of shape {tuple(image.shape)}")
+            P, D = self.model.patch_size, self.model.embedding_dim
+            e = Entry(use_graph=self.use_graph, x=torch.empty(cropped_shape(tuple(image.shape), P), device=image.device, dtype=dtype))
+            e.low = DINOv2Lowering(image.device, dtype, cache, "merged")
+            T = 1 + self.model.num_registers + (image.shape[2] // P) * (image.shape[3] // P)
+            e.out = torch.empty(image.shape[0] * token_rows(T), D, device=image.device, dtype=dtype)
+            e.low.lower(self.model, e.x, e.out)
+            native.replay(e.low.prologue)  # the position table, resampled to this grid
+            return e
+
+        e = self.programs.get(self._weights_version(), (tuple(image.shape), dtype, image.device), build)
         if e is None:
-            try:
-                _expect(image.dim() == 4, f"input of shape {tuple(image.shape)}")
-                P, D = self.model.patch_size, self.model.embedding_dim
-                x = torch.empty(cropped_shape(tuple(image.shape), P), device=image.device, dtype=dtype)
-                low = DINOv2Lowering(image.device, dtype, self.cache, "merged")
-                T = 1 + self.model.num_registers + (image.shape[2] // P) * (image.shape[3] // P)
-                out = torch.empty(image.shape[0] * token_rows(T), D, device=image.device, dtype=dtype)
-                low.lower(self.model, x, out)
-            except Unsupported as err:
-                warnings.warn(f"CompiledDINOv2: {err}; running the stock forward", RuntimeWarning, stacklevel=2)
-                self.bad_keys.add(key)
-                return self._stock(image)
-            if edited:  # (a further shape of the same weights adds packs and must not sweep the other programs' away)
-                self.cache.sweep()
-            native.replay(low.prologue)  # the position table, resampled to this grid
-            self.lowerings += 1
-            e = _Entry(x, out, low, Program(low.step, self.use_graph, low=low))
-            while len(self.entries) >= MAX_PROGRAMS:
-                self.entries.pop(next(iter(self.entries)))
-            self.entries[key] = e
-        self.program = e.program
-        self.stats = dict(e.low.stats, step_ops=launches(e.low.step), prologue_ops=launches(e.low.prologue), pool_bytes=e.low.step_pool.bytes(), lowerings=self.lowerings,
-                          tokens=e.low.T, token_rows=e.low.Tp)
+            return self._stock(image)
+        self.stats = dict(e.stats, prologue_ops=launches(e.low.prologue), lowerings=self.lowerings, tokens=e.low.T, token_rows=e.low.Tp)
         e.x.copy_(image[:, :, : e.x.shape[2], : e.x.shape[3]])  # the strided convolution drops a remainder of H, W: so does this copy
         e.program.run()
         return e.out.view(image.shape[0], e.low.Tp, -1)[:, : e.low.T].clone()

@@ -40,10 +40,10 @@ from torch import Tensor
 from .. import native
 from ..fluxion.tree import tree_epoch
 from .packing import LinSpec, PackCache, Unsupported, _expect, cname, isa, kids, launches
+from .program import MAX_PROGRAMS, Entry, HasPrograms, ProgramCache
 
 LLM_TOKENS = ("adapted_cross_attention_block", "llm_text_embedding")
 ELLA_TOKENS = ("ella", "latents")
-MAX_PROGRAMS = 8  # lowered (B, T) shapes kept per CompiledELLA
 
 
 def pad64(n: int) -> int:
@@ -285,28 +285,20 @@ class EllaLowering:
 
 
 # ------------------------------------------------------------------------------------------------ the resampler alone
-class _Entry:
-    def __init__(self, io: Any, llm: Tensor, out: Tensor, Nl: int, low: Any, program: Any) -> None:
-        self.io, self.llm, self.out, self.Nl, self.low, self.program = io, llm, out, Nl, low, program
-
-
-class CompiledELLA:
+class CompiledELLA(HasPrograms):
     """`fast = CompiledELLA(ella); latents = fast(timestep, llm_text_embedding)`: what the reference leaves in context ella.latents after
     `ella.set_context("diffusion", {"timestep": timestep}); ella.set_context("adapted_cross_attention_block", {"llm_text_embedding": e}); ella(x)`.
     timestep: one value shared by the batch, or [B, 1] / [B] per-row values; llm_text_embedding [B, T, input_dim] -> [B, num_latents, out_width].
     One lowered program and one HIP graph per (B, T), the last MAX_PROGRAMS shapes kept; the input projection (prompt side) runs again only when
-    another embedding tensor is given.  An in-place edit of a weight re-lowers.  There is no fallback: a tree the lowering does not cover raises
-    Unsupported."""
+    another embedding tensor is given.  There is no fallback: a tree the lowering does not cover raises Unsupported."""
 
     def __init__(self, ella: Any, dtype: Optional[torch.dtype] = None, use_graph: bool = True) -> None:
         native.load()
         self.ella = ella
         self.dtype = dtype
         self.use_graph = use_graph
-        self.cache = PackCache()
-        self.entries: dict[Any, _Entry] = {}
-        self.version: Any = None
-        self.lowerings, self.prologue_runs = 0, 0
+        self.programs = ProgramCache("CompiledELLA", MAX_PROGRAMS)
+        self.prologue_runs = 0
         self.prompt: Any = None
         self.stats: dict[str, Any] = {}
 
@@ -315,7 +307,7 @@ class CompiledELLA:
 
     @torch.no_grad()
     def __call__(self, timestep: Any, llm_text_embedding: Tensor) -> Tensor:
-        from .compiled import Program, _ident
+        from .compiled import _ident
         from .unet_lowering import UNetLowering
 
         e_in = llm_text_embedding
@@ -323,32 +315,25 @@ class CompiledELLA:
         B, T, Din = e_in.shape
         dev = e_in.device
         dtype = self.dtype or next(p.dtype for p in self.ella.parameters())
-        version = self._version()
-        if version != self.version:
-            self.entries.clear()
-            self.cache.used.clear()
-            self.version, self.prompt = version, None
+
+        def build(cache: PackCache) -> Entry:
+            e = Entry(use_graph=self.use_graph, io=SimpleNamespace(timestep=torch.empty(B, device=dev, dtype=torch.float32), timesteps=None, step_rows=None))
+            e.llm = torch.zeros(B * pad64(T), Din, device=dev, dtype=dtype)
+            e.low = UNetLowering(dev, dtype, cache, "merged")
+            e.low.io = e.io
+            e.low.step_tokens = set()
+            with e.low.in_step():
+                e.out, e.Nl = e.low.ella(self.ella, e.llm, T, B)
+            return e
+
         key = (B, T, Din, dtype, dev)
-        e = self.entries.get(key)
-        if e is None:
-            Tp = pad64(T)
-            io = SimpleNamespace(timestep=torch.empty(B, device=dev, dtype=torch.float32), timesteps=None, step_rows=None)
-            llm = torch.zeros(B * Tp, Din, device=dev, dtype=dtype)
-            low = UNetLowering(dev, dtype, self.cache, "merged")
-            low.io = io
-            low.step_tokens = set()
-            try:
-                with low.in_step():
-                    out, Nl = low.ella(self.ella, llm, T, B)
-            except Unsupported as err:
-                warnings.warn(f"CompiledELLA: {err}", RuntimeWarning, stacklevel=2)
-                raise
-            self.cache.sweep()
-            self.lowerings += 1
-            e = _Entry(io, llm, out, Nl, low, Program(low.step, self.use_graph, low=low))
-            while len(self.entries) >= MAX_PROGRAMS:
-                self.entries.pop(next(iter(self.entries)))
-            self.entries[key] = e
+        lowerings = self.lowerings
+        try:
+            e = self.programs.get(self._version(), key, build)
+        except Unsupported as err:
+            warnings.warn(f"CompiledELLA: {err}", RuntimeWarning, stacklevel=2)
+            raise
+        if self.lowerings != lowerings:  # a fresh program: its token buffer is empty, whatever tensor was staged last
             self.prompt = None
         ts = torch.as_tensor(timestep, dtype=torch.float32).to(dev).reshape(-1)
         assert ts.numel() in (1, B), f"timestep of {ts.numel()} values for a batch of {B}"
@@ -360,7 +345,7 @@ class CompiledELLA:
             self.prologue_runs += 1
             self.prompt, self._prompt_ref = prompt, e_in  # (the tensor itself: a live tensor's address cannot be recycled, see compiled._ident)
         e.program.run()
-        self.stats = dict(e.low.stats, step_ops=launches(e.low.step), prologue_ops=launches(e.low.prologue), lowerings=self.lowerings, prologue_runs=self.prologue_runs,
+        self.stats = dict(e.stats, prologue_ops=launches(e.low.prologue), lowerings=self.lowerings, prologue_runs=self.prologue_runs,
                           pool_bytes=e.low.step_pool.bytes() + e.low.prologue_pool.bytes())
         Nlp = e.out.shape[0] // B
         return e.out.view(B, Nlp, -1)[:, : e.Nl].clone()

@@ -22,8 +22,8 @@ from torch import Tensor
 
 from .. import native
 from ..fluxion.tree import tree_epoch
-from .compiled import Program
-from .packing import PackCache, _expect, isa, kids, launches
+from .packing import PackCache, _expect, isa, kids
+from .program import Entry, HasPrograms, ProgramCache
 from .text import TextLowering
 
 
@@ -180,7 +180,7 @@ class ImagePromptLowering(TextLowering):
             self.pool.put(t)
 
 
-class CompiledImagePrompt:
+class CompiledImagePrompt(HasPrograms):
     """`fast = CompiledImagePrompt(clip_image_encoder, image_proj); tokens = fast(image)` ==
     `cat(image_proj(zeros_like(e)), image_proj(e))` with `e = clip_image_encoder(image)` -- what
     `IPAdapter.compute_clip_image_embedding` hands to `set_clip_image_embedding` for one image per prompt.
@@ -190,38 +190,37 @@ class CompiledImagePrompt:
         native.load()
         self.encoder, self.image_proj = encoder, image_proj
         self.lora_mode, self.use_graph = lora_mode, use_graph
-        self.cache = PackCache()
-        self.key: Any = None
+        self.programs = ProgramCache("CompiledImagePrompt")
         self.stats: dict[str, Any] = {}
 
     @torch.no_grad()
     def __call__(self, image: Tensor) -> Tensor:
         dev, dtype = self.encoder.device, self.encoder.dtype
         B = image.shape[0]
-        key = (tree_epoch(), tuple(image.shape), dtype, dev)
-        if key != self.key:
-            self.x = torch.empty(tuple(image.shape), device=dev, dtype=dtype)
-            self.cls_rows = torch.zeros(B, device=dev, dtype=torch.int32)
-            od = self.encoder.output_dim
-            self.both = torch.zeros(2 * B, od, device=dev, dtype=dtype)  # rows [0, B) stay zero: the negative prompt
-            low = ImagePromptLowering(dev, dtype, self.cache, self.lora_mode)
-            low.lower_image_encoder(self.encoder, self.x, self.cls_rows, self.both[B:])
-            self.tokens = None
+
+        def build(cache: PackCache) -> Entry:
+            e = Entry(use_graph=self.use_graph, tokens=None)
+            e.x = torch.empty(tuple(image.shape), device=dev, dtype=dtype)
+            e.cls_rows = torch.zeros(B, device=dev, dtype=torch.int32)
+            e.both = torch.zeros(2 * B, self.encoder.output_dim, device=dev, dtype=dtype)  # rows [0, B) stay zero: the negative prompt
+            e.low = ImagePromptLowering(dev, dtype, cache, self.lora_mode)
+            e.low.lower_image_encoder(self.encoder, e.x, e.cls_rows, e.both[B:])
             if self.image_proj is not None:
                 nt, ct = self.image_proj.num_tokens, self.image_proj.clip_text_embedding_dim
-                self.tokens = torch.empty(2 * B * nt, ct, device=dev, dtype=dtype)
-                low.lower_image_projection(self.image_proj, self.both, self.tokens)
-            self.cache.sweep()
-            self.low, self.key, self.program = low, key, Program(low.step, self.use_graph, low=low)
-            self.stats = dict(low.stats, step_ops=launches(low.step), pool_bytes=low.step_pool.bytes())
-        self.x.copy_(image)
-        self.program.run()
-        if self.tokens is None:
-            return self.both[B:].clone()
-        return self.tokens.view(2 * B, self.image_proj.num_tokens, -1).clone()
+                e.tokens = torch.empty(2 * B * nt, ct, device=dev, dtype=dtype)
+                e.low.lower_image_projection(self.image_proj, e.both, e.tokens)
+            return e
+
+        e = self.programs.get((tree_epoch(),), (tuple(image.shape), dtype, dev), build)
+        self.stats = e.stats
+        e.x.copy_(image)
+        e.program.run()
+        if e.tokens is None:
+            return e.both[B:].clone()
+        return e.tokens.view(2 * B, self.image_proj.num_tokens, -1).clone()
 
 
-class CompiledImagePromptPlus:
+class CompiledImagePromptPlus(HasPrograms):
     """Fine-grained ("plus") IP-Adapter image prompt: `fast = CompiledImagePromptPlus(grid_image_encoder, perceiver_resampler);
     tokens = fast(image)` == `cat(resampler(enc(zeros_like(image))), resampler(enc(image)))` -- what
     `IPAdapter.compute_clip_image_embedding` returns for a fine-grained adapter (image_prompt.py:516-525): (2B, 16, 2048)
@@ -231,25 +230,26 @@ class CompiledImagePromptPlus:
         native.load()
         self.encoder, self.resampler = grid_encoder, resampler
         self.lora_mode, self.use_graph = lora_mode, use_graph
-        self.cache = PackCache()
-        self.key: Any = None
+        self.programs = ProgramCache("CompiledImagePromptPlus")
         self.stats: dict[str, Any] = {}
 
     @torch.no_grad()
     def __call__(self, image: Tensor) -> Tensor:
         dev, dtype = self.encoder.device, self.encoder.dtype
         B = image.shape[0]
-        key = (tree_epoch(), tuple(image.shape), dtype, dev)
-        if key != self.key:
-            self.x = torch.zeros((2 * B,) + tuple(image.shape[1:]), device=dev, dtype=dtype)  # rows [0, B) stay zero: the negative prompt's image
-            low = ImagePromptLowering(dev, dtype, self.cache, self.lora_mode)
-            feats, L = low.lower_grid_encoder(self.encoder, self.x)
+
+        def build(cache: PackCache) -> Entry:
+            e = Entry(use_graph=self.use_graph)
+            e.x = torch.zeros((2 * B,) + tuple(image.shape[1:]), device=dev, dtype=dtype)  # rows [0, B) stay zero: the negative prompt's image
+            e.low = ImagePromptLowering(dev, dtype, cache, self.lora_mode)
+            feats, L = e.low.lower_grid_encoder(self.encoder, e.x)
             nt, od = self.resampler.num_tokens, self.resampler.output_dim
-            self.tokens = torch.empty(2 * B * nt, od, device=dev, dtype=dtype)
-            low.lower_perceiver(self.resampler, feats, 2 * B, L, self.tokens)
-            self.cache.sweep()
-            self.low, self.key, self.program = low, key, Program(low.step, self.use_graph, low=low)
-            self.stats = dict(low.stats, step_ops=launches(low.step), pool_bytes=low.step_pool.bytes())
-        self.x[B:].copy_(image)
-        self.program.run()
-        return self.tokens.view(2 * B, self.resampler.num_tokens, -1).clone()
+            e.tokens = torch.empty(2 * B * nt, od, device=dev, dtype=dtype)
+            e.low.lower_perceiver(self.resampler, feats, 2 * B, L, e.tokens)
+            return e
+
+        e = self.programs.get((tree_epoch(),), (tuple(image.shape), dtype, dev), build)
+        self.stats = e.stats
+        e.x[B:].copy_(image)
+        e.program.run()
+        return e.tokens.view(2 * B, self.resampler.num_tokens, -1).clone()

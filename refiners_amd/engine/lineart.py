@@ -24,7 +24,6 @@ out_channels != 1, in_channels > 4, an InstanceNorm2d with affine parameters or 
 """
 from __future__ import annotations
 
-import warnings
 from typing import Any, Optional
 
 import torch
@@ -32,11 +31,9 @@ from torch import Tensor
 
 from .. import native
 from ..fluxion.tree import ChainError, tree_epoch
-from .compiled import Program
 from .lowering import Lowering
-from .packing import Act, ConvSpec, PackCache, Unsupported, _expect, cname, isa, kids, launches
-
-MAX_PROGRAMS = 8  # lowered shapes kept per CompiledInformativeDrawings
+from .packing import Act, ConvSpec, PackCache, _expect, cname, isa, kids
+from .program import MAX_PROGRAMS, Entry, HasPrograms, ProgramCache
 
 
 # ------------------------------------------------------------------------------------------------ host helpers
@@ -239,32 +236,19 @@ def lower(model: Any, image: Tensor, out: Tensor, cache: Optional[PackCache] = N
     return low
 
 
-class _Entry:
-    """One lowered shape: its static input / output buffers, lowering and program."""
-
-    def __init__(self, x: Tensor, out: Tensor, low: LineartLowering, program: Program) -> None:
-        self.x, self.out, self.low, self.program = x, out, low, program
-
-
-class CompiledInformativeDrawings:
+class CompiledInformativeDrawings(HasPrograms):
     """`fast = CompiledInformativeDrawings(model); y = fast(image)` == `model(image)`: [B, in_channels, H, W] -> [B, 1, H', W'], H' = 4 ceil(ceil(H / 2) / 2).
-    One lowered program and one HIP graph per (B, H, W, dtype), the last MAX_PROGRAMS kept: a repeat call of a shape replays its graph.  `dtype`
-    (default: the tree's) is the compute dtype.  An in-place edit of a weight re-lowers (only what changed is re-packed).  A size the model itself
-    refuses raises before anything is launched; a tree the lowering does not cover runs its stock forward behind a RuntimeWarning
-    (`stats["whole_fallback"]`)."""
+    One lowered program and one HIP graph per (B, H, W, dtype), the last MAX_PROGRAMS kept.  `dtype` (default: the tree's) is the compute dtype.
+    A size the model itself refuses raises before anything is launched; a tree the lowering does not cover runs its stock forward behind a
+    RuntimeWarning (`stats["whole_fallback"]`)."""
 
     def __init__(self, model: Any, use_graph: bool = True, dtype: Optional[torch.dtype] = None) -> None:
         native.load()
         self.model = model
         self.dtype = dtype
         self.use_graph = use_graph
-        self.cache = PackCache()
-        self.entries: dict[Any, _Entry] = {}
-        self.version: Any = None
-        self.bad_keys: set = set()
-        self.lowerings = 0
+        self.programs = ProgramCache("CompiledInformativeDrawings", MAX_PROGRAMS, fallback=True)
         self.stats: dict[str, Any] = {"fallback_nodes": [], "step_ops": 0, "whole_fallback": False}
-        self.program: Optional[Program] = None
 
     def _tree_dtype(self) -> torch.dtype:
         return next(p.dtype for p in self.model.parameters())
@@ -276,43 +260,24 @@ class CompiledInformativeDrawings:
     @torch.no_grad()
     def __call__(self, image: Tensor) -> Tensor:
         dtype = self.dtype or self._tree_dtype()
-        version = self._weights_version()
-        edited = version != self.version
-        if edited:  # every program goes; the first lowering after it sweeps the packs nothing uses any more
-            self.entries.clear()
-            self.bad_keys.clear()
-            self.cache.used.clear()
-            self.version = version
-        key = (tuple(image.shape), dtype, image.device)
-        if key in self.bad_keys:
-            return self._stock(image)
-        e = self.entries.get(key)
+
+        def build(cache: PackCache) -> Entry:
+            _expect(image.dim() == 4, f"input of shape {tuple(image.shape)}")
+            B, _c, H, W = image.shape
+            check_size(H, W, sum(1 for c in kids(self.model) if isa(c, "Residual")))
+            e = Entry(use_graph=self.use_graph, x=torch.empty(tuple(image.shape), device=image.device, dtype=dtype))
+            e.out = torch.empty((B, 1) + out_size(H, W), device=image.device, dtype=dtype)
+            e.low = lower(self.model, e.x, e.out, cache)
+            return e
+
+        e = self.programs.get(self._weights_version(), (tuple(image.shape), dtype, image.device), build)
         if e is None:
-            try:
-                _expect(image.dim() == 4, f"input of shape {tuple(image.shape)}")
-                B, _c, H, W = image.shape
-                check_size(H, W, sum(1 for c in kids(self.model) if isa(c, "Residual")))
-                x = torch.empty(tuple(image.shape), device=image.device, dtype=dtype)
-                out = torch.empty((B, 1) + out_size(H, W), device=image.device, dtype=dtype)
-                low = lower(self.model, x, out, self.cache)
-            except Unsupported as err:
-                warnings.warn(f"CompiledInformativeDrawings: {err}; running the stock forward", RuntimeWarning, stacklevel=2)
-                self.bad_keys.add(key)
-                return self._stock(image)
-            if edited:  # (a further shape of the same weights adds packs and must not sweep the other programs' away)
-                self.cache.sweep()
-            self.lowerings += 1
-            e = _Entry(x, out, low, Program(low.step, self.use_graph, low=low))
-            while len(self.entries) >= MAX_PROGRAMS:
-                self.entries.pop(next(iter(self.entries)))
-            self.entries[key] = e
-        self.program = e.program
-        self.stats = dict(e.low.stats, step_ops=launches(e.low.step), pool_bytes=e.low.step_pool.bytes(), lowerings=self.lowerings, whole_fallback=False)
+            return self._stock(image)
+        self.stats = dict(e.stats, lowerings=self.lowerings, whole_fallback=False)
         e.x.copy_(image)
         e.program.run()
         return e.out.clone()
 
     def _stock(self, image: Tensor) -> Tensor:
-        self.program = None
         self.stats = {"fallback_nodes": [cname(self.model)], "step_ops": 0, "whole_fallback": True, "lowerings": self.lowerings}
         return self.model(image.to(self._tree_dtype()))

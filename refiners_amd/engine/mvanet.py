@@ -27,7 +27,6 @@ training mode, num_heads != 1, an embedding width that is not 128, LoRA on any l
 from __future__ import annotations
 
 import math
-import warnings
 from types import SimpleNamespace
 from typing import Any, Optional
 
@@ -36,8 +35,8 @@ from torch import Tensor
 
 from .. import native
 from ..fluxion.tree import tree_epoch
-from .compiled import Program
-from .packing import Act, ConvSpec, PackCache, Unsupported, _expect, cname, isa, kids, launches
+from .packing import Act, ConvSpec, PackCache, _expect, cname, isa, kids
+from .program import Entry, HasPrograms, ProgramCache
 from .swin import SwinLowering, output_shapes
 
 EMB = 128  # the head width the decoder's attention runs at (mi355x_attention_general instance (4, 8))
@@ -465,8 +464,8 @@ def _on(bn: Any, device: torch.device) -> Any:
     return SimpleNamespace(eps=bn.eps, **{k: getattr(bn, k).detach().to(device) for k in ("weight", "bias", "running_mean", "running_var")})
 
 
-class _Compiled:
-    """Shared by the block and whole-net entry points: one program per (tree state, input shape, dtype, weight versions), replayed as a HIP graph."""
+class _Compiled(HasPrograms):
+    """Shared by the block and whole-net entry points: one program, replayed as a HIP graph."""
 
     what = ""
 
@@ -475,10 +474,7 @@ class _Compiled:
         self.tree = tree
         self.dtype = dtype
         self.use_graph = use_graph
-        self.cache = PackCache()
-        self.key: Any = None
-        self.bad_key: Any = None
-        self.lowerings = 0
+        self.programs = ProgramCache(self.what, fallback=True)
         self.stats: dict[str, Any] = {}
         self.keep_intermediates = False  # CompiledMVANet: also return the Pyramid and RearrangeMultiView outputs, in `intermediates`
         self.intermediates: dict[str, Tensor] = {}
@@ -504,28 +500,23 @@ class _Compiled:
     @torch.no_grad()
     def __call__(self, x: Tensor) -> Tensor:
         dtype = self.dtype or self._tree_dtype()
-        key = (tree_epoch(), tuple(x.shape), dtype, x.device, self._weights_version(dtype), self._modes(), self.keep_intermediates)
-        if key == self.bad_key:
+
+        def build(cache: PackCache) -> Entry:
+            e = Entry(use_graph=self.use_graph, x=torch.empty(tuple(x.shape), device=x.device, dtype=dtype))
+            e.low = MVANetLowering(x.device, dtype, cache, "merged")
+            e.low.taps = {} if self.keep_intermediates else None
+            e.out = self._lower(e.low, e.x)
+            return e
+
+        version = (tree_epoch(), self._weights_version(dtype), self._modes(), self.keep_intermediates)
+        e = self.programs.get(version, (tuple(x.shape), dtype, x.device), build)
+        if e is None:
             return self._stock(x)
-        if key != self.key:
-            try:
-                self.x = torch.empty(tuple(x.shape), device=x.device, dtype=dtype)
-                low = MVANetLowering(x.device, dtype, self.cache, "merged")
-                low.taps = {} if self.keep_intermediates else None
-                self.out = self._lower(low, self.x)
-            except Unsupported as e:
-                warnings.warn(f"{self.what}: {e}; running the stock forward", RuntimeWarning, stacklevel=2)
-                self.bad_key = key
-                return self._stock(x)
-            self.cache.sweep()
-            self.low, self.key = low, key
-            self.lowerings += 1
-            self.program = Program(low.step, self.use_graph, low=low)
-            self.stats = dict(low.stats, step_ops=launches(low.step), pool_bytes=low.step_pool.bytes(), lowerings=self.lowerings)
-        self.x.copy_(x)
-        self.program.run()
-        self.intermediates = {k: a.image().permute(0, 3, 1, 2).clone() for k, a in (self.low.taps or {}).items()}
-        return self.out.clone()
+        self.stats = dict(e.stats, lowerings=self.lowerings)
+        e.x.copy_(x)
+        e.program.run()
+        self.intermediates = {k: a.image().permute(0, 3, 1, 2).clone() for k, a in (e.low.taps or {}).items()}
+        return e.out.clone()
 
 
 class CompiledMVANet(_Compiled):

@@ -31,9 +31,9 @@ from torch import Tensor
 
 from .. import native
 from ..fluxion.tree import tree_epoch
-from .compiled import Program
 from .lowering_blocks import BlockLowering as Lowering
-from .packing import Act, PackCache, Unsupported, _expect, cname, isa, kids, launches
+from .packing import Act, PackCache, Unsupported, _expect, cname, isa, kids
+from .program import Entry, HasPrograms, ProgramCache
 
 
 class SAMLowering(Lowering):
@@ -266,7 +266,7 @@ class SAMLowering(Lowering):
         self.pool.put(z1)
 
 
-class CompiledSAMViT:
+class CompiledSAMViT(HasPrograms):
     """`fast = CompiledSAMViT(vit); embedding = fast(image)` == `vit(image)`; with a SAMViTAdapter injected the early ViT
     embedding is written to context "hq_sam".early_vit_embedding exactly like the SetContext node does."""
 
@@ -275,8 +275,7 @@ class CompiledSAMViT:
         self.vit = vit
         self.lora_mode = lora_mode
         self.use_graph = use_graph
-        self.cache = PackCache()
-        self.key: Any = None
+        self.programs = ProgramCache("CompiledSAMViT")
         self.stats: dict[str, Any] = {}
 
     def _hook(self) -> Optional[Any]:
@@ -288,24 +287,25 @@ class CompiledSAMViT:
     @torch.no_grad()
     def __call__(self, image: Tensor) -> Tensor:
         dtype = self.vit.dtype
-        key = (tree_epoch(), tuple(image.shape), dtype, image.device)
-        if key != self.key:
+
+        def build(cache: PackCache) -> Entry:
             B = image.shape[0]
-            self.x = torch.empty(tuple(image.shape), device=image.device, dtype=dtype)
+            e = Entry(x=torch.empty(tuple(image.shape), device=image.device, dtype=dtype))
             neck_conv = [m for m in self.vit.modules() if isa(m, "Conv2d")][-1]
             gh, gw = image.shape[2] // self.vit.patch_size, image.shape[3] // self.vit.patch_size
-            self.out = torch.empty(B, neck_conv.out_channels, gh, gw, device=image.device, dtype=dtype)
-            self.early = torch.empty(B, gh, gw, self.vit.embedding_dim, device=image.device, dtype=dtype) if self._hook() is not None else None
-            low = SAMLowering(image.device, dtype, self.cache, self.lora_mode)
-            low.lower(self.vit, self.x, self.out, self.early)
-            self.cache.sweep()
-            self.low, self.key = low, key
+            e.out = torch.empty(B, neck_conv.out_channels, gh, gw, device=image.device, dtype=dtype)
+            e.early = torch.empty(B, gh, gw, self.vit.embedding_dim, device=image.device, dtype=dtype) if self._hook() is not None else None
+            e.low = SAMLowering(image.device, dtype, cache, self.lora_mode)
+            e.low.lower(self.vit, e.x, e.out, e.early)
             # the torch fallback of an attention (un-merged LoRA, odd shapes) allocates: not capturable
-            self.program = Program(low.step, self.use_graph and not low.stats["fallback_nodes"], low=low)
-            self.stats = dict(low.stats, step_ops=launches(low.step), pool_bytes=low.step_pool.bytes())
-        self.x.copy_(image)
-        self.program.run()
+            e.use_graph = self.use_graph and not e.low.stats["fallback_nodes"]
+            return e
+
+        e = self.programs.get((tree_epoch(),), (tuple(image.shape), dtype, image.device), build)
+        self.stats = e.stats
+        e.x.copy_(image)
+        e.program.run()
         hook = self._hook()
         if hook is not None:
-            hook(self.early.clone())  # SetContext.__call__: stores into the parent's context, as the unfused tree does
-        return self.out.clone()
+            hook(e.early.clone())  # SetContext.__call__: stores into the parent's context, as the unfused tree does
+        return e.out.clone()

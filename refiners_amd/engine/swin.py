@@ -19,7 +19,6 @@ with fewer than 2 windows per side (the reference itself raises on a shifted sta
 """
 from __future__ import annotations
 
-import warnings
 from typing import Any, Optional
 
 import torch
@@ -27,9 +26,9 @@ from torch import Tensor
 
 from .. import native
 from ..fluxion.tree import tree_epoch
-from .compiled import Program
 from .lowering_blocks import BlockLowering as Lowering
-from .packing import PackCache, Unsupported, _expect, cname, isa, kids, launches
+from .packing import PackCache, _expect, cname, isa, kids
+from .program import Entry, HasPrograms, ProgramCache
 
 HEAD_DIM = 32    # the only head width mi355x_window_attention instantiates
 MAX_TOKENS = 144  # tokens per window (ws <= 12)
@@ -267,7 +266,7 @@ def output_shapes(swin: Any, B: int, S: int) -> list[tuple[int, int, int, int]]:
     return shapes
 
 
-class CompiledSwinTransformer:
+class CompiledSwinTransformer(HasPrograms):
     """`fast = CompiledSwinTransformer(swin); maps = fast(x)` == `swin(x)`: the tuple (stage_n, ..., stage_1, patch_embedding) of NCHW maps.
     One program per (batch, side), replayed as a HIP graph.  `dtype` (default: the tree's) is the compute dtype.  A tree the lowering does
     not cover runs its stock forward behind a RuntimeWarning."""
@@ -277,10 +276,7 @@ class CompiledSwinTransformer:
         self.swin = swin
         self.dtype = dtype
         self.use_graph = use_graph
-        self.cache = PackCache()
-        self.key: Any = None
-        self.bad_key: Any = None
-        self.lowerings = 0
+        self.programs = ProgramCache("CompiledSwinTransformer", fallback=True)
         self.stats: dict[str, Any] = {}
 
     def _tree_dtype(self) -> torch.dtype:
@@ -295,28 +291,22 @@ class CompiledSwinTransformer:
     @torch.no_grad()
     def __call__(self, image: Tensor) -> tuple[Tensor, ...]:
         dtype = self.dtype or self._tree_dtype()
-        key = (tree_epoch(), tuple(image.shape), dtype, image.device, self._weights_version(dtype))
-        if key == self.bad_key:
+
+        def build(cache: PackCache) -> Entry:
+            _expect(image.dim() == 4 and image.shape[2] == image.shape[3], f"non-square input {tuple(image.shape)}")
+            e = Entry(use_graph=self.use_graph, x=torch.empty(tuple(image.shape), device=image.device, dtype=dtype))
+            e.outs = [torch.empty(s, device=image.device, dtype=dtype) for s in output_shapes(self.swin, image.shape[0], image.shape[2])]
+            e.low = SwinLowering(image.device, dtype, cache, "merged")
+            e.low.lower(self.swin, e.x, e.outs)
+            return e
+
+        e = self.programs.get((tree_epoch(), self._weights_version(dtype)), (tuple(image.shape), dtype, image.device), build)
+        if e is None:
             return self._stock(image)
-        if key != self.key:
-            try:
-                _expect(image.dim() == 4 and image.shape[2] == image.shape[3], f"non-square input {tuple(image.shape)}")
-                self.x = torch.empty(tuple(image.shape), device=image.device, dtype=dtype)
-                self.outs = [torch.empty(s, device=image.device, dtype=dtype) for s in output_shapes(self.swin, image.shape[0], image.shape[2])]
-                low = SwinLowering(image.device, dtype, self.cache, "merged")
-                low.lower(self.swin, self.x, self.outs)
-            except Unsupported as e:
-                warnings.warn(f"CompiledSwinTransformer: {e}; running the stock forward", RuntimeWarning, stacklevel=2)
-                self.bad_key = key
-                return self._stock(image)
-            self.cache.sweep()
-            self.low, self.key = low, key
-            self.lowerings += 1
-            self.program = Program(low.step, self.use_graph, low=low)
-            self.stats = dict(low.stats, step_ops=launches(low.step), pool_bytes=low.step_pool.bytes(), lowerings=self.lowerings)
-        self.x.copy_(image)
-        self.program.run()
-        return tuple(o.clone() for o in self.outs)
+        self.stats = dict(e.stats, lowerings=self.lowerings)
+        e.x.copy_(image)
+        e.program.run()
+        return tuple(o.clone() for o in e.outs)
 
     def _stock(self, image: Tensor) -> tuple[Tensor, ...]:
         return self.swin(image.to(self._tree_dtype()))

@@ -16,7 +16,6 @@ picture side the factor does not divide, channel counts whose rows are not whole
 """
 from __future__ import annotations
 
-import warnings
 from typing import Any, Optional
 
 import torch
@@ -24,11 +23,9 @@ from torch import Tensor
 
 from .. import native
 from ..fluxion.tree import tree_epoch
-from .compiled import Program
 from .lowering import Lowering
-from .packing import Act, PackCache, Unsupported, _expect, cname, isa, kids, launches
-
-MAX_PROGRAMS = 8  # lowered shapes kept per CompiledT2IConditionEncoder
+from .packing import Act, PackCache, _expect, cname, isa, kids
+from .program import MAX_PROGRAMS, Entry, HasPrograms, ProgramCache
 
 
 def _pair(v: Any) -> tuple:
@@ -129,33 +126,20 @@ def lower(encoder: Any, picture: Tensor, outs: list[Tensor], dtype: Optional[tor
     return low
 
 
-class _Entry:
-    """One lowered shape: its static input / output buffers, lowering and program."""
-
-    def __init__(self, x: Tensor, outs: list[Tensor], low: T2ILowering, program: Program) -> None:
-        self.x, self.outs, self.low, self.program = x, outs, low, program
-
-
-class CompiledT2IConditionEncoder:
+class CompiledT2IConditionEncoder(HasPrograms):
     """`fast = CompiledT2IConditionEncoder(adapter.condition_encoder); features = fast(condition)` == `adapter.compute_condition_features(condition)`:
     [B, in_channels, H, W] -> the tuple of four NCHW contiguous feature maps that `adapter.set_condition_features` and
-    `CompiledUNet.set_inputs(t2i_features=)` take.  One lowered program and one HIP graph per (B, H, W, dtype), the last MAX_PROGRAMS kept: a
-    repeat call of a shape replays its graph.  `dtype` (default: the tree's) is the compute dtype; a float32 picture is read as it is.  An
-    in-place edit of a weight re-lowers.  A tree or a picture size the lowering does not cover runs the stock forward behind a RuntimeWarning
-    (`stats["whole_fallback"]`)."""
+    `CompiledUNet.set_inputs(t2i_features=)` take.  One lowered program and one HIP graph per (B, H, W, dtype), the last MAX_PROGRAMS kept.
+    `dtype` (default: the tree's) is the compute dtype; a float32 picture is read as it is.  A tree or a picture size the lowering does not
+    cover runs the stock forward behind a RuntimeWarning (`stats["whole_fallback"]`)."""
 
     def __init__(self, encoder: Any, use_graph: bool = True, dtype: Optional[torch.dtype] = None) -> None:
         native.load()
         self.encoder = encoder
         self.dtype = dtype
         self.use_graph = use_graph
-        self.cache = PackCache()
-        self.entries: dict[Any, _Entry] = {}
-        self.version: Any = None
-        self.bad_keys: set = set()
-        self.lowerings = 0
+        self.programs = ProgramCache("CompiledT2IConditionEncoder", MAX_PROGRAMS, fallback=True)
         self.stats: dict[str, Any] = {"fallback_nodes": [], "step_ops": 0, "whole_fallback": False}
-        self.program: Optional[Program] = None
 
     def _tree_dtype(self) -> torch.dtype:
         return next(p.dtype for p in self.encoder.parameters())
@@ -167,43 +151,25 @@ class CompiledT2IConditionEncoder:
     @torch.no_grad()
     def __call__(self, condition: Tensor) -> tuple[Tensor, ...]:
         dtype = self.dtype or self._tree_dtype()
-        version = self._weights_version()
-        edited = version != self.version
-        if edited:
-            self.entries.clear()
-            self.bad_keys.clear()
-            self.cache.used.clear()
-            self.version = version
-        key = (tuple(condition.shape), condition.dtype, dtype, condition.device)
-        if key in self.bad_keys:
-            return self._stock(condition)
-        e = self.entries.get(key)
+
+        def build(cache: PackCache) -> Entry:
+            _expect(condition.dim() == 4, f"input of shape {tuple(condition.shape)}")
+            B, _c, Hp, Wp = condition.shape
+            shapes = feature_shapes(self.encoder, B, Hp, Wp)
+            e = Entry(use_graph=self.use_graph)
+            e.x = torch.empty(tuple(condition.shape), device=condition.device, dtype=torch.float32 if condition.dtype == torch.float32 else dtype)
+            e.outs = [torch.empty(s, device=condition.device, dtype=dtype) for s in shapes]
+            e.low = lower(self.encoder, e.x, e.outs, dtype, cache)
+            return e
+
+        e = self.programs.get(self._weights_version(), (tuple(condition.shape), condition.dtype, dtype, condition.device), build)
         if e is None:
-            try:
-                _expect(condition.dim() == 4, f"input of shape {tuple(condition.shape)}")
-                B, _c, Hp, Wp = condition.shape
-                shapes = feature_shapes(self.encoder, B, Hp, Wp)
-                x = torch.empty(tuple(condition.shape), device=condition.device, dtype=torch.float32 if condition.dtype == torch.float32 else dtype)
-                outs = [torch.empty(s, device=condition.device, dtype=dtype) for s in shapes]
-                low = lower(self.encoder, x, outs, dtype, self.cache)
-            except Unsupported as err:
-                warnings.warn(f"CompiledT2IConditionEncoder: {err}; running the stock forward", RuntimeWarning, stacklevel=2)
-                self.bad_keys.add(key)
-                return self._stock(condition)
-            if edited:
-                self.cache.sweep()
-            self.lowerings += 1
-            e = _Entry(x, outs, low, Program(low.step, self.use_graph, low=low))
-            while len(self.entries) >= MAX_PROGRAMS:
-                self.entries.pop(next(iter(self.entries)))
-            self.entries[key] = e
-        self.program = e.program
-        self.stats = dict(e.low.stats, step_ops=launches(e.low.step), pool_bytes=e.low.step_pool.bytes(), lowerings=self.lowerings, whole_fallback=False)
+            return self._stock(condition)
+        self.stats = dict(e.stats, lowerings=self.lowerings, whole_fallback=False)
         e.x.copy_(condition)
         e.program.run()
         return tuple(o.clone() for o in e.outs)
 
     def _stock(self, condition: Tensor) -> tuple[Tensor, ...]:
-        self.program = None
         self.stats = {"fallback_nodes": [cname(self.encoder)], "step_ops": 0, "whole_fallback": True, "lowerings": self.lowerings}
         return tuple(self.encoder(condition.to(self._tree_dtype())))

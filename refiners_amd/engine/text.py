@@ -24,9 +24,9 @@ from torch import Tensor
 
 from .. import native
 from ..fluxion.tree import tree_epoch
-from .compiled import Program
 from .lowering_blocks import BlockLowering as Lowering
-from .packing import PackCache, _expect, cname, isa, kids, launches
+from .packing import PackCache, _expect, cname, isa, kids
+from .program import Entry, HasPrograms, ProgramCache
 
 
 class TextLowering(Lowering):
@@ -176,7 +176,7 @@ def _as_tokens(t: Tensor, device: torch.device) -> Tensor:
     return t.to(device=device, dtype=torch.int32).contiguous()
 
 
-class CompiledDoubleTextEncoder:
+class CompiledDoubleTextEncoder(HasPrograms):
     """`fast = CompiledDoubleTextEncoder(double_text_encoder); emb, pooled = fast(prompts)` == `double_text_encoder(prompts)`
     ((B, 77, 2048), (B, 1280)); `fast(tokens=(tokens_l, tokens_g))` skips the host tokenizers."""
 
@@ -185,8 +185,7 @@ class CompiledDoubleTextEncoder:
         self.enc = enc
         self.lora_mode = lora_mode
         self.use_graph = use_graph
-        self.cache = PackCache()
-        self.key: Any = None
+        self.programs = ProgramCache("CompiledDoubleTextEncoder")
         self.stats: dict[str, Any] = {}
 
     def tokenizers(self) -> tuple[Any, Any]:
@@ -205,30 +204,32 @@ class CompiledDoubleTextEncoder:
         dev, dtype = self.enc.device, self.enc.dtype
         tok_l, tok_g = _as_tokens(tokens[0], dev), _as_tokens(tokens[1], dev)
         B, L = tok_l.shape
-        key = (tree_epoch(), B, L, dtype, dev)
-        if key != self.key:
-            self.tok_l = torch.empty(B * L, device=dev, dtype=torch.int32)
-            self.tok_g = torch.empty(B * L, device=dev, dtype=torch.int32)
-            self.eot = torch.empty(B, device=dev, dtype=torch.int32)
+
+        def build(cache: PackCache) -> Entry:
+            e = Entry(use_graph=self.use_graph)
+            e.tok_l = torch.empty(B * L, device=dev, dtype=torch.int32)
+            e.tok_g = torch.empty(B * L, device=dev, dtype=torch.int32)
+            e.eot = torch.empty(B, device=dev, dtype=torch.int32)
             cl = next(p for n, p in self.enc.named_parameters() if "CLIPTextEncoderL" in n and p.dim() == 2).shape[1]
             cg = next(p for n, p in self.enc.named_parameters() if "CLIPTextEncoderG" in n and p.dim() == 2).shape[1]
-            self.emb = torch.empty(B * L, cl + cg, device=dev, dtype=dtype)
-            self.pooled = torch.empty(B, cg, device=dev, dtype=dtype)
-            low = TextLowering(dev, dtype, self.cache, self.lora_mode)
-            low.lower_double(self.enc, self.tok_l, self.tok_g, self.eot, B, L, self.emb, self.pooled)
-            self.cache.sweep()
-            self.low, self.key, self.program = low, key, Program(low.step, self.use_graph, low=low)
-            self.stats = dict(low.stats, step_ops=launches(low.step), pool_bytes=low.step_pool.bytes())
-        self.tok_l.copy_(tok_l.reshape(-1))
-        self.tok_g.copy_(tok_g.reshape(-1))
+            e.emb = torch.empty(B * L, cl + cg, device=dev, dtype=dtype)
+            e.pooled = torch.empty(B, cg, device=dev, dtype=dtype)
+            e.low = TextLowering(dev, dtype, cache, self.lora_mode)
+            e.low.lower_double(self.enc, e.tok_l, e.tok_g, e.eot, B, L, e.emb, e.pooled)
+            return e
+
+        e = self.programs.get((tree_epoch(),), (B, L, dtype, dev), build)
+        self.stats = e.stats
+        e.tok_l.copy_(tok_l.reshape(-1))
+        e.tok_g.copy_(tok_g.reshape(-1))
         # first end-of-text position per prompt (TextEncoderWithPooling.set_end_of_text_index, xl/text_encoder.py:48-51)
         first = (tok_g == tg.end_of_text_token_id).to(torch.int32).argmax(dim=1).to(torch.int32)
-        self.eot.copy_(first + torch.arange(B, device=dev, dtype=torch.int32) * L)
-        self.program.run()
-        return self.emb.view(B, L, -1).clone(), self.pooled.clone()
+        e.eot.copy_(first + torch.arange(B, device=dev, dtype=torch.int32) * L)
+        e.program.run()
+        return e.emb.view(B, L, -1).clone(), e.pooled.clone()
 
 
-class CompiledTextEncoder:
+class CompiledTextEncoder(HasPrograms):
     """`fast = CompiledTextEncoder(clip_text_encoder); hidden = fast(prompts)` == `clip_text_encoder(prompts)` (B, 77, C)."""
 
     def __init__(self, enc: Any, lora_mode: str = "merged", use_graph: bool = True) -> None:
@@ -236,8 +237,7 @@ class CompiledTextEncoder:
         self.enc = enc
         self.lora_mode = lora_mode
         self.use_graph = use_graph
-        self.cache = PackCache()
-        self.key: Any = None
+        self.programs = ProgramCache("CompiledTextEncoder")
         self.stats: dict[str, Any] = {}
 
     @torch.no_grad()
@@ -247,15 +247,17 @@ class CompiledTextEncoder:
         dev, dtype = self.enc.device, self.enc.dtype
         tok = _as_tokens(tokens, dev)
         B, L = tok.shape
-        key = (tree_epoch(), B, L, dtype, dev)
-        if key != self.key:
-            self.tok = torch.empty(B * L, device=dev, dtype=torch.int32)
-            self.out = torch.empty(B * L, self.enc.embedding_dim, device=dev, dtype=dtype)
-            low = TextLowering(dev, dtype, self.cache, self.lora_mode)
-            low.lower_encoder(self.enc, self.tok, B, L, self.out)
-            self.cache.sweep()
-            self.low, self.key, self.program = low, key, Program(low.step, self.use_graph, low=low)
-            self.stats = dict(low.stats, step_ops=launches(low.step), pool_bytes=low.step_pool.bytes())
-        self.tok.copy_(tok.reshape(-1))
-        self.program.run()
-        return self.out.view(B, L, -1).clone()
+
+        def build(cache: PackCache) -> Entry:
+            e = Entry(use_graph=self.use_graph)
+            e.tok = torch.empty(B * L, device=dev, dtype=torch.int32)
+            e.out = torch.empty(B * L, self.enc.embedding_dim, device=dev, dtype=dtype)
+            e.low = TextLowering(dev, dtype, cache, self.lora_mode)
+            e.low.lower_encoder(self.enc, e.tok, B, L, e.out)
+            return e
+
+        e = self.programs.get((tree_epoch(),), (B, L, dtype, dev), build)
+        self.stats = e.stats
+        e.tok.copy_(tok.reshape(-1))
+        e.program.run()
+        return e.out.view(B, L, -1).clone()
